@@ -1,6 +1,8 @@
 """bench.py — RIPAgent.act() throughput on MI355X (BASELINE.json metric).
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full          (+ every secondary line listed below)
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
   python bench.py --gpus 8 ...                     (self-spawns 8 ranks under torch.distributed.run)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
@@ -17,7 +19,13 @@ selection with the [30,3] float64 interpolation (R11 on the device) and the copy
 to pinned host memory.  Every observation is one `RIPAgent.act()` call: value = obs_batch * steps * n_gpus / time.
 `hbm_resident` is the same step on observations already in HBM without R11 (R2..R10: last round's headline).
 
-Multi-GPU (one process per GPU, RCCL).  `--gpus N` with NO `--mode` (what the driver runs) times the
+A plain run sets up, warms up, times exactly `--steps` steps once and prints the headline line: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` and the configuration.  `--dump-outputs DIR` then also writes what the
+last timed step handed its caller, the [B,30,3] float64 plans on the host, as DIR/plans.npy (inputs are seeded: the same
+arguments give the same observations).  Everything else below (`--repeats` regions, whose default becomes 3, the
+secondary lines, the roofline, the CPU baseline, the compositions of `--gpus N`) runs only with `--full`.
+
+Multi-GPU (one process per GPU, RCCL).  `--gpus N --full` with NO `--mode` times the
 observation-parallel replicas for `value` AND, in the same invocation, the two compositions that need a collective, and
 prints ONE line: `candidate_parallel` (north_star's "candidate throughput": N candidates per rank, one RCCL all-gather
 of (best loss, plan) per step), `model_parallel` (when K % N == 0: K / N models per rank, one all-gather of the per-model
@@ -30,7 +38,7 @@ aborts unless every rank was seen by a collective.  An explicit `--mode` runs on
   models      `--models` K split over the ranks, gradient-mode model parallelism: per Adam step ONE all-gather of
               the (q_k, dq_k/dy) block (BASELINE configs[3]: --models 8 --candidates 512)       -> "strong"
 
-The JSON line also carries
+With `--full` the JSON line also carries
   roofline      — the dominant kernel (plan search): executed MFMA flops (exact instruction count of this launch
                   configuration, from the kernel's own per-step selection trace) / the dense-f16 MFMA peak (`frac`; the
                   kernel is instruction-issue bound: `bound` = "issue"), `matrix_pipe_busy` = the fraction of the launch
@@ -287,6 +295,23 @@ def _free_port():
     return s.getsockname()[1]
 
 
+def _library_is_current(entry):
+  """build()'s own up-to-date test, without writing: every object and the library exist and their digests (flags,
+  source, headers) match the manifest the last build() left."""
+  headers = sorted(os.path.join(entry.CSRC, f) for f in os.listdir(entry.CSRC) if f.endswith(".h"))
+  headers.append(os.path.join(entry.ROOT, "include", "rip_hip.h"))
+  try:
+    with open(os.path.join(entry.OBJDIR, "manifest.json")) as f:
+      manifest = json.load(f)
+  except (OSError, ValueError):
+    return False
+  sources = entry._sources()
+  if not os.path.exists(entry.LIB) or manifest.get("__lib__") != entry._digest([os.path.join(entry.CSRC, s) for s in sources] + headers):
+    return False
+  return all(manifest.get(s) == entry._digest([os.path.join(entry.CSRC, s)] + headers) and
+             os.path.exists(os.path.join(entry.OBJDIR, s + ".o")) for s in sources)
+
+
 def _self_spawn(args):
   """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU."""
   n = torch.cuda.device_count()
@@ -302,7 +327,8 @@ def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--gpus", type=int, default=1)
   ap.add_argument("--steps", type=int, default=20)
-  ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps; value = the median one")
+  ap.add_argument("--repeats", type=int, default=None,
+                  help="timed regions of --steps steps; value = the median one (default: 1, with --full 3)")
   ap.add_argument("--warmup", type=int, default=5)
   ap.add_argument("--obs-batch", type=int, default=DEFAULT_OBS_BATCH, help="observations (= act() calls) per step per GPU")
   ap.add_argument("--encoder-dtype", default="bf16", choices=["bf16", "fp32"],
@@ -313,14 +339,20 @@ def main():
   ap.add_argument("--algorithm", default="WCM")
   ap.add_argument("--search-steps", type=int, default=10)
   ap.add_argument("--mode", default=None, choices=["replay", "candidates", "models"],
-                  help="default: replay; with --gpus N > 1 and no --mode the candidate- / model-parallel compositions run too")
+                  help="default: replay; with --gpus N > 1, --full and no --mode the candidate- / model-parallel compositions run too")
   ap.add_argument("--cpu-seconds", type=float, default=5.0)
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--no-extras", action="store_true", help="skip the secondary lines (online, pcie, scoring, fp32, C=4)")
   ap.add_argument("--online-calls", type=int, default=1000)
+  ap.add_argument("--full", action="store_true",
+                  help="also the secondary lines, roofline, CPU baseline and --gpus N compositions (default: headline only)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the last timed step computed as DIR/<name>.npy")
   if len(sys.argv) > 1 and sys.argv[1] == "--cpu-baseline-worker":
     return _cpu_baseline_worker(sys.argv[2:])
   args = ap.parse_args()
+  if args.repeats is None:
+    args.repeats = 3 if args.full else 1
   explicit_mode = args.mode is not None
   if args.mode is None:
     args.mode = "replay"
@@ -363,7 +395,9 @@ def main():
   args.backend_seen, args.world_seen = backend_seen, world_seen
 
   import __graft_entry__ as entry
-  if rank == 0:
+  # build() rewrites its manifest on every call, and the tree may be another user's read-only built checkout: call it
+  # only when it has something to compile (a missing library, an edited source or header, other flags)
+  if rank == 0 and not _library_is_current(entry):
     entry.build()
   if dist is not None:
     dist.barrier()
@@ -396,7 +430,7 @@ def main():
   seeds = [100 + k for k in range(K)]
 
   if args.mode != "replay":
-    line = _bench_parallel_mode(args, args.mode, rank, world, dev, dist, timed, args.steps, args.warmup)
+    line = _bench_parallel_mode(args, args.mode, rank, world, dev, dist, timed, args.steps, args.warmup, dump=args.dump_outputs)
     if rank == 0:
       print(json.dumps(line))
     dist.barrier()
@@ -477,25 +511,64 @@ def main():
   prime()
   # `--repeats` timed regions of EXACTLY `--steps` steps each (barrier + synchronize on both sides of every one; the warm-up
   # runs once, in front of the first): `value` is the MEDIAN region — one 20-step region is 0.08 s, and single samples of
-  # it spread by ~0.6 % — min / max are reported beside it.
+  # it spread by ~0.6 % — min / max are reported beside it.  The per-step events feed the roofline
+  # (--full) only.
   unit_step = make_unit_step(enc_dtype)
   regions = []
   for r in range(max(1, args.repeats)):
-    ev_r = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
+    ev_r = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)] if args.full else None
     regions.append((timed(unit_step, args.steps, args.warmup if r == 0 else 0, ev_r), ev_r))
   order = sorted(range(len(regions)), key=lambda i: regions[i][0])
   elapsed, events = regions[order[len(order) // 2]]
   region_rates = [B * args.steps * world / el for el, _ in regions]
   assert torch.isfinite(plan).all() and bool(np.isfinite(plan30_host[0].numpy()).all())
-  # the [30,3] float64 plans on the host are the reference's R11 of the device's [4,2] plans, bit for bit
-  from oatomobile_amd.agents import interpolate_plan
-  last = (tick[0] - 1) & 1
-  r11_ok = all(np.array_equal(plan30_host[last].numpy()[i], interpolate_plan(plan.cpu().numpy()[i])) for i in (0, B // 2, B - 1))
-  enc_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in events]))
-  search_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in events]))
+  last = (tick[0] - 1) & 1  # the host slot of the last timed step: what act() handed the controller
+  if rank == 0 and args.dump_outputs:
+    _dump_outputs(args.dump_outputs, plans=plan30_host[last].numpy())
   calls = B * args.steps * world
   value = calls / elapsed
   h2d_bytes = sum(t.numel() * 4 for t in pinned[0])
+  head = {
+      "metric": "RIPAgent.act() calls/sec (K=%d, %d plans, 200x200 BEV)" % (K, N),
+      "value": value,
+      "unit": "calls/s",
+      "n_gpus": world,
+      "steps": args.steps,
+      "warmup": args.warmup,
+      "ms_per_step": 1e3 * elapsed / args.steps,
+      "repeats": {"n": len(region_rates), "value_is": "median of n timed regions of `steps` steps each",
+                  "calls_per_s": [round(v, 1) for v in region_rates], "min": min(region_rates), "max": max(region_rates)},
+      "higher_is_better": True,
+      "scaling": "weak",
+      "vs_baseline": None,
+      "dtype": ("bf16 encoder (bf16 storage, fp32 accumulate) + " if args.encoder_dtype == "bf16" else "fp32 encoder + ") +
+               "flow/search: fp32 accumulate, GRU/head contractions as two-term binary16 (22-bit) operands on f16 MFMA "
+               "(the waypoint / bias terms as three-term, 33-bit operands)",
+      "data": "synthetic",
+      "config": {"workload": "BASELINE configs[2]: RIPAgent K=%d %s, N=%d candidate plans, %d Adam steps, 200x200x%d BEV, "
+                             "%s encoder + fp32 flow" % (K, args.algorithm, N, S, C, args.encoder_dtype),
+                 "obs_per_step_per_gpu": B, "models": K, "candidates": N, "bev_channels": C,
+                 "parallelism": "observation-parallel replicas x%d (no data-path collective)" % world},
+      "unit_of_work": {"covers": "R1..R11: pinned-host float32 observations -> H2D (copy stream, double-buffered) -> transform -> "
+                         "K encoders + merger -> plan search -> selection + [30,3] float64 interpolation -> D2H to pinned host",
+                       "h2d_MB_per_step": h2d_bytes / 1e6, "d2h_KB_per_step": B * 30 * 3 * 8 / 1e3},
+      "backend": args.backend_seen,
+      "world_size_seen": args.world_seen,
+  }
+  if not args.full:
+    if rank == 0:
+      print(json.dumps(head))
+    if dist is not None:
+      dist.barrier()
+      dist.destroy_process_group()
+    return
+
+  # ---------------- --full: everything beyond the headline ----------------
+  # the [30,3] float64 plans on the host are the reference's R11 of the device's [4,2] plans, bit for bit
+  from oatomobile_amd.agents import interpolate_plan
+  r11_ok = all(np.array_equal(plan30_host[last].numpy()[i], interpolate_plan(plan.cpu().numpy()[i])) for i in (0, B // 2, B - 1))
+  enc_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in events]))
+  search_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in events]))
 
   # the same step without R1 / R11 (observations resident in HBM, [B,4,2] plans back): last round's `value`
   batches = [tuple(torch.from_numpy(a).to(dev) for a in hb) for hb in host_batches]
@@ -765,37 +838,13 @@ def main():
       except Exception as exc:  # noqa: BLE001
         roof["encoder"]["kernels"] = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:200])}
     roof.update(extras)
+    head["unit_of_work"]["r11_bit_identical_to_reference_arithmetic"] = bool(r11_ok)
     out = {
-        "metric": "RIPAgent.act() calls/sec (K=%d, %d plans, 200x200 BEV)" % (K, N),
-        "value": value,
-        "unit": "calls/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "repeats": {"n": len(region_rates), "value_is": "median of n timed regions of `steps` steps each",
-                    "calls_per_s": [round(v, 1) for v in region_rates], "min": min(region_rates), "max": max(region_rates)},
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": ("bf16 encoder (bf16 storage, fp32 accumulate) + " if args.encoder_dtype == "bf16" else "fp32 encoder + ") +
-                 "flow/search: fp32 accumulate, GRU/head contractions as two-term binary16 (22-bit) operands on f16 MFMA "
-                 "(the waypoint / bias terms as three-term, 33-bit operands)",
-        "data": "synthetic",
-        "config": {"workload": "BASELINE configs[2]: RIPAgent K=%d %s, N=%d candidate plans, %d Adam steps, 200x200x%d BEV, "
-                               "%s encoder + fp32 flow" % (K, args.algorithm, N, S, C, args.encoder_dtype),
-                   "obs_per_step_per_gpu": B, "models": K, "candidates": N, "bev_channels": C,
-                   "parallelism": "observation-parallel replicas x%d (no data-path collective)" % world},
+        **head,
         "roofline": roof,
-        "unit_of_work": {"covers": "R1..R11: pinned-host float32 observations -> H2D (copy stream, double-buffered) -> transform -> "
-                           "K encoders + merger -> plan search -> selection + [30,3] float64 interpolation -> D2H to pinned host",
-                         "h2d_MB_per_step": h2d_bytes / 1e6, "d2h_KB_per_step": B * 30 * 3 * 8 / 1e3,
-                         "r11_bit_identical_to_reference_arithmetic": bool(r11_ok)},
         "hbm_resident": hbm_line,
         "hbm_resident_512": hbm512,
         "two_handles_two_streams": pipelined,
-        "backend": args.backend_seen,
-        "world_size_seen": args.world_seen,
         "candidate_parallel": par_lines.get("candidates"),
         "model_parallel": par_lines.get("models") if world > 1 else None,
         "rccl": rccl,
@@ -819,6 +868,22 @@ def main():
 
 
 # ------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(directory, **arrays):
+  """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 as computed).  An array past DUMP_LIMIT_BYTES is
+  cut to a fixed, seeded sample of its rows, so that two builds still compare row for row."""
+  os.makedirs(directory, exist_ok=True)
+  for name, a in arrays.items():
+    a = np.ascontiguousarray(a)
+    assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+      keep = DUMP_LIMIT_BYTES // (a.nbytes // len(a))
+      a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+    np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def _bench_online(args, models, dev, host_batch):
   """The reference's usage pattern: one `agent(observation)` per tick — host numpy dict in, [30,3] numpy out, with
   the H2D of the 320 KB BEV, every kernel and the D2H + sync inside each call."""
@@ -1023,9 +1088,10 @@ def _rccl_seen(dist, dev, world):
           "librccl_mapped": mapped}
 
 
-def _bench_parallel_mode(args, mode, rank, world, dev, dist, timed, steps, warmup):
+def _bench_parallel_mode(args, mode, rank, world, dev, dist, timed, steps, warmup, dump=None):
   """`candidates` | `models`: the compositions of oatomobile_amd/distributed.py over RCCL.  Every rank
-  calls this; rank 0 gets the result line (a dict), the others None."""
+  calls this; rank 0 gets the result line (a dict), the others None.  `dump`: a directory for rank 0's [B,4,2] plans of
+  the last timed step (--dump-outputs)."""
   from oatomobile_amd import ImitativeModel
   from oatomobile_amd import distributed as D
   K, N, B, C, S = args.models, args.candidates, args.obs_batch, args.channels, args.search_steps
@@ -1060,6 +1126,8 @@ def _bench_parallel_mode(args, mode, rank, world, dev, dist, timed, steps, warmu
            "runs on every rank after the gather" % (K, world))
     scaling, n_total, collectives = "strong", N, S + 1
   elapsed = timed(step, steps, warmup)
+  if dump and rank == 0:
+    _dump_outputs(dump, plans=out_host.numpy())
   # the distributed result against the world-1 composition of the same search on rank 0 (same candidate stream)
   if mode == "candidates":
     plan_d = cp(lidar, vec, goal)[0]

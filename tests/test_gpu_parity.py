@@ -1871,7 +1871,7 @@ def test_bench_two_ranks_share_one_gpu():
   """`python bench.py --gpus 2` (self-spawn under torch.distributed.run, barrier + max-over-ranks timing, rank 0
   prints the line) on a ONE-GPU box: both ranks on cuda:0 and gloo instead of RCCL (RCCL refuses two ranks on one
   device).  Checks the world > 1 code path and the JSON contract, not the numbers."""
-  rec = _run_bench_two_ranks(["--obs-batch", "32"])
+  rec = _run_bench_two_ranks(["--obs-batch", "32", "--full"])
   assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["warmup"] == 1 and rec["scaling"] == "weak"
   assert rec["value"] > 0 and abs(rec["value"] - 2 * 32 * 3 / (rec["ms_per_step"] * 3e-3)) < 1e-6 * rec["value"]
   assert rec["roofline"]["frac"] is None or 0 < rec["roofline"]["frac"] < 1
@@ -1895,13 +1895,54 @@ def test_bench_two_gpus_over_rccl():
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
   env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "RIP_BENCH_SHARE_GPU", "RIP_BENCH_BACKEND")}
   out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--obs-batch", "64",
-                        "--no-cpu-baseline", "--no-extras"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--no-extras", "--full"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-3000:]
   rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
   assert rec["n_gpus"] == 2 and rec["backend"] == "nccl" and rec["world_size_seen"] == 2
   assert rec["rccl"] == {"backend": "nccl", "ranks_seen": 2, "all_reduce_of_ones": 2.0, "librccl_mapped": True}
   for key in ("candidate_parallel", "model_parallel"):
     assert "error" not in rec[key] and rec[key]["max_abs_plan_diff_vs_single_gpu"] <= 1e-4, rec[key]
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+  """A plain `bench.py --gpus 1` times exactly `--steps` steps once and prints the headline line alone (the secondary
+  lines need `--full`); `--dump-outputs` writes the last timed step's [B,30,3] float64 plans, the same from run to run
+  (the observations are seeded)."""
+  import json, subprocess, sys
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "RIP_BENCH_SHARE_GPU", "RIP_BENCH_BACKEND")}
+  plans = []
+  for run in range(2):
+    d = tmp_path / ("run%d" % run)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--obs-batch", "32", "--dump-outputs", str(d)], cwd=root, env=env, capture_output=True, text=True,
+                         timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["higher_is_better"] is True and rec["unit"] == "calls/s" and rec["dtype"] and rec["metric"]
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["repeats"]["n"] == 1
+    assert rec["value"] > 0 and abs(rec["value"] - 32 * 3 / (rec["ms_per_step"] * 3e-3)) < 1e-6 * rec["value"]
+    assert not {"roofline", "hbm_resident", "online", "fp32_parity", "cpu_baseline"} & set(rec), sorted(rec)
+    assert sorted(os.listdir(d)) == ["plans.npy"]
+    p = np.load(d / "plans.npy")
+    assert p.dtype == np.float64 and p.shape == (32, 30, 3) and np.isfinite(p).all()
+    plans.append(p)
+  np.testing.assert_array_equal(plans[0], plans[1])
+  # and they are the plans of the observations the last timed step planned: bench.py draws two seeded host batches and
+  # alternates them step by step, so after 1 + 3 steps the last one ran on the second batch
+  import bench
+  from oatomobile_amd import ImitativeModel, RIPAgent
+  dev = torch.device("cuda", 0)
+  rng = np.random.default_rng(1000)
+  batches = [bench.synth_batch(rng, 32, 2) for _ in range(2)]
+  agent = RIPAgent(None, algorithm="WCM", models=[ImitativeModel.synthetic(100 + k, in_channels=2, max_batch=1) for k in range(4)],
+                   num_candidates=128, num_steps=10, max_batch=32, seed=0, device=dev, encoder_dtype="bf16")
+  want = [agent.plan_batch(*(torch.from_numpy(a).to(dev) for a in b), interpolate=True).cpu().numpy() for b in batches]
+  np.testing.assert_allclose(plans[0], want[1], rtol=0, atol=TOL)
+  assert np.abs(plans[0] - want[0]).max() > 100 * TOL  # (the other batch's plans are far off: the check can tell them apart)
 
 
 @pytest.mark.gpu

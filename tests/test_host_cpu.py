@@ -465,3 +465,23 @@ def test_packed_replay_cache_round_trip(tmp_path):
              player_future=np.zeros((80, 3), np.float32))
   with pytest.raises(ValueError, match="256 distinct"):
     replay.pack_cache(ep2.files(), str(tmp_path / "cache2"))
+
+
+def test_bench_dump_outputs_writes_npy_and_samples_past_the_cap(tmp_path, monkeypatch):
+  """bench.py --dump-outputs: one <name>.npy per array as computed; an array past the size cap becomes the same seeded
+  sample of its rows on every call, so that two builds still compare row for row."""
+  import bench
+  a = np.arange(100 * 3, dtype=np.float64).reshape(100, 3)
+  bench._dump_outputs(str(tmp_path / "whole"), plans=a)
+  np.testing.assert_array_equal(np.load(tmp_path / "whole" / "plans.npy"), a)
+  monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * a[0].nbytes)
+  for d in ("s0", "s1"):
+    bench._dump_outputs(str(tmp_path / d), plans=a)
+  s0, s1 = np.load(tmp_path / "s0" / "plans.npy"), np.load(tmp_path / "s1" / "plans.npy")
+  assert s0.shape == (10, 3) and s0.dtype == np.float64
+  np.testing.assert_array_equal(s0, s1)
+  rows = s0[:, 0].astype(int) // 3
+  assert np.all(np.diff(rows) > 0)  # distinct rows, in order
+  np.testing.assert_array_equal(s0, a[rows])
+  with pytest.raises(AssertionError):
+    bench._dump_outputs(str(tmp_path / "ints"), plans=np.zeros((2, 3), np.int32))

@@ -2,9 +2,9 @@
 # time and WRITE_SIZE / FETCH_SIZE against the 8-wave default.  Restores the normal build.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R
-export RIP_EXTRA_HIPCC_FLAGS="-DRIP_FORCE_WPB=4"  # (bench.py rebuilds when the flags differ from the last build)
+export RIP_EXTRA_HIPCC_FLAGS="-DRIP_FORCE_WPB=4"  # (build() below rebuilds when the flags differ from the last build)
 python -c "import __graft_entry__ as g; g.build()" > /dev/null 2>&1
-BENCH="python bench.py --no-cpu-baseline --no-extras --steps 10 --warmup 3"
+BENCH="python bench.py --full --no-cpu-baseline --no-extras --steps 10 --warmup 3"
 $BENCH 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('WPB=4 forced: search ms', round(d['roofline']['ms_per_launch'],3), 'calls/s', round(d['value']))"
 for c in WRITE_SIZE FETCH_SIZE; do

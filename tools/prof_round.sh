@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof
 rm -rf $O; mkdir -p $O
 cd $R
-BENCH="python bench.py --no-cpu-baseline --no-extras --steps 10 --warmup 3"
+BENCH="python bench.py --full --no-cpu-baseline --no-extras --steps 10 --warmup 3"
 # 1. per-kernel time of the bench command
 rocprofv3 --kernel-trace --stats -d $O/stats --output-format csv -- $BENCH > $O/stats.log 2>&1
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv 2>/dev/null

@@ -22,8 +22,8 @@
  *     hipFree / hipMemcpy / device synchronisation (safe under stream capture).
  *     All device scratch is allocated by rip_create from (max_batch,
  *     max_candidates); a call that exceeds it returns RIP_ESTATE.
- *     rip_create / rip_destroy / rip_load_model / rip_train_create / _destroy
- *     are the only ones that allocate or copy synchronously.  NULL = the null stream.
+ *     rip_create / rip_destroy / rip_load_model / rip_train_create /
+ *     rip_cil_train_create / rip_train_destroy are the only ones that allocate or copy synchronously.  NULL = the null stream.
  *   - a handle is bound to one device: every entry point that takes a handle
  *     makes that device current for the duration of the call and restores the
  *     caller's current device before returning.  The stateless entry points
@@ -291,6 +291,28 @@ int rip_train_adam(float* params_dev, const float* grads_dev, float* m_dev, floa
  * moves a per-channel gradient by ~1/(B*H*W).  Tests read the masks back through this call to compare like with like.) */
 int rip_train_peek(rip_trainer* t, int layer, int what, int B, float* dst_dev, size_t dst_numel, rip_stream_t stream);
 int rip_train_num_layers(const rip_trainer* t);
+
+/* The CIL training step, oatomobile/baselines/torch/cil/train.py:168-190 (train_step) and :208-219 (evaluate_step):
+ *   predictions = BehaviouralModel(**batch) with T = horizon_T decoder steps (MobileNetV2 in train mode as above),
+ *   loss = mean_b sum_{t,d} |predictions - player_future[..., :2]| (nn.L1Loss summed over [-2,-1], averaged over the
+ *   batch), loss.backward(); the caller clips and steps Adam with rip_train_adam (weight_decay is a real flag here).
+ * Layout: rip_cil_train_numel(C) floats in the order of the reference BehaviouralModel.state_dict() minus the
+ * num_batches_tracked counters: the encoder and classifier exactly as in the DIM layout, then _merger._model.{0,2,4}
+ * (first layer 134 wide: features 128 | velocity 3 | is_at_traffic_light | traffic_light_state | mode),
+ * _decoder.weight_ih [192,2], weight_hh [192,64], bias_ih, bias_hh (GRUCell, gates r, z, n), _output.weight [2,64],
+ * _output.bias [2].  The handle is a rip_trainer: rip_train_destroy / _trainable_mask / _peek / _num_layers and
+ * rip_train_adam work on it unchanged; rip_train_forward_backward refuses it, and rip_cil_train_forward_backward
+ * refuses a DIM handle (RIP_EINVAL).
+ * rip_cil_train_forward_backward: visual_dev [B,C,100,100], vec_dev [B,6] (velocity 3, is_at_traffic_light,
+ *   traffic_light_state, mode), target_dev [B,T,2], dropout_mask_dev [B,1280] or NULL, train != 0: BatchNorm batch
+ *   statistics with the running-stat update (as batch_stats above), 0: eval mode.  Writes *loss_dev, pred_dev [B,T,2]
+ *   (optional) and grads_dev (running-statistic slots: 0); grads_dev == NULL: forward only (loss and predictions).
+ *   The L1 derivative at pred == target is 0 (torch's sign).  Enqueues on `stream` without synchronising. */
+size_t rip_cil_train_numel(int in_channels);
+int rip_cil_train_create(rip_trainer** out, int in_channels, int horizon_T, int max_batch, int device);
+int rip_cil_train_forward_backward(rip_trainer* t, float* params_dev, float* grads_dev, const float* visual_dev,
+                                   const float* vec_dev, const float* target_dev, const float* dropout_mask_dev, int B,
+                                   int train, float* loss_dev, float* pred_dev, rip_stream_t stream);
 
 /* Implementation knobs (results are identical within the parity tolerance; tests run every setting).
  *   RIP_OPT_SEARCH_KERNEL: 0 = auto (the split-f16 phase-sequential kernel when B*N >= 1280 and N % 16 == 0, else

@@ -77,6 +77,10 @@ SIGNATURES = [
     ("rip_train_adam", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_float, c_float, c_float,
       c_void_p]),
+    ("rip_cil_train_numel", c_size_t, [c_int]),
+    ("rip_cil_train_create", c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
+    ("rip_cil_train_forward_backward", c_int,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 ]
 ABI_VERSION = 4
 

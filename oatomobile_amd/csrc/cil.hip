@@ -9,12 +9,16 @@
 // whole decode is ~0.5 MFLOP per sample; it is launch latency, not throughput, that matters here, so everything after
 // the encoder is this ONE kernel.
 //
+// Training (cil/train.py:168-190): cil_train_kernel below is this decoder's forward with a tape, the L1 loss
+// cotangent and the backward-through-time; the encoder / merger halves of the step are the DIM trainer's (train.hip).
+//
 // Weight blob (fp32, arch.py:cil_decoder_spec order): W0[64][134] b0[64] W1[64][64] b1[64] W2[64][64] b2[64]
 // W_ih[192][2] W_hh[192][64] b_ih[192] b_hh[192] W_out[2][64] b_out[2].  torch.nn.GRUCell gate order (r, z, n).
 #include <hip/hip_runtime.h>
 
 #include "flow.h"
 #include "flow_math.h"
+#include "train.h"
 
 namespace rip {
 
@@ -120,6 +124,147 @@ __global__ __launch_bounds__(WAVES * 64) void cil_decode_kernel(const float* __r
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Training: the decoder of BehaviouralModel (cil/model.py:104-125) with L1 loss (cil/train.py:176-180) forward and
+// backward-through-time, one wavefront per batch row, lane j = hidden unit j (cil_decode_kernel's layout).
+//   forward   cil_decode_kernel's arithmetic, operation for operation (W_hh rows read from LDS instead of registers:
+//             the same values in the same fma order), taping per step into the row's records (r, z, n, W_hn h + b_hn,
+//             dpred lane-locally in the dgi / dgh slots, h_prev, h, x_in in their own), so T is unbounded;
+//   loss      l1_rows[b] = sum_t sum_d |pred - target|,  dpred = sign(pred - target) / B (sign(0) = 0: torch's L1
+//             backward);
+//   backward  reverse t: g_x(t) = dpred_t + g_x(t+1) + W_ih^T dgi(t+1) (the residual x_t = x_{t-1} + out(h_t), and x_t
+//             is the input of step t+1), g_h(t) = W_out^T g_x(t) + z(t+1) g_h(t+1) + W_hh^T dgh(t+1), then the GRUCell
+//             adjoint (gate order r, z, n; the n gate's hidden-side pre-activation gradient is r * dn_pre);
+//             dz = g_h(-1), the adjoint of the initial hidden state (the merger output).
+// Records per (row, t) (CIL_TRAIN_REC floats, train.h): dgi 192 | dgh 192 | h_prev 64 | h 64 | x_in 2 | dout 2; the
+// trainer forms dW_ih = dgi^T x_in, dW_hh = dgh^T h_prev, dW_out = dout^T h as GEMMs over the B*T records and the
+// biases as their column sums.  W_hh^T: lane i needs column i, so W_hh is staged in LDS with rows padded to 65 floats
+// (both the row-per-lane forward read and the column-per-lane backward read are bank-conflict free); no weight lives
+// in registers across the kernel.
+// ------------------------------------------------------------------------------------------
+constexpr int TW = 4;           // waves (rows) per workgroup
+constexpr int WHH_LD = H + 1;   // LDS row pitch of W_hh
+constexpr int REC_DGI = 0, REC_DGH = 3 * H, REC_HPREV = 6 * H, REC_H = 7 * H, REC_XIN = 8 * H, REC_DOUT = 8 * H + 2;
+static_assert(REC_DOUT + 2 == CIL_TRAIN_REC, "record layout");
+
+__device__ __forceinline__ float signf_(float e) { return e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f); }
+
+__global__ __launch_bounds__(TW * 64) void cil_train_kernel(
+    const float* __restrict__ wih, const float* __restrict__ whh, const float* __restrict__ bih,
+    const float* __restrict__ bhh, const float* __restrict__ wout, const float* __restrict__ bout,
+    const float* __restrict__ zin, const float* __restrict__ target, int B, int T, float inv_b, int backward,
+    float* __restrict__ pred, float* __restrict__ l1_rows, float* __restrict__ dz, float* __restrict__ rec) {
+  __shared__ float ws[3 * H * WHH_LD];
+  __shared__ float bc[TW][3 * H];  // per wave: h (forward) / (dr, dz, dghn) (backward) broadcast
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int e = tid; e < 3 * H * H; e += TW * 64) ws[(e >> 6) * WHH_LD + (e & 63)] = whh[e];
+  __syncthreads();
+  const int b = blockIdx.x * TW + wave;
+  if (b >= B) return;
+  float* a = bc[wave];
+  const float* wr = ws + (0 * H + lane) * WHH_LD;
+  const float* wz = ws + (1 * H + lane) * WHH_LD;
+  const float* wn = ws + (2 * H + lane) * WHH_LD;
+  const float wir0 = wih[(0 * H + lane) * 2], wir1 = wih[(0 * H + lane) * 2 + 1];
+  const float wiz0 = wih[(1 * H + lane) * 2], wiz1 = wih[(1 * H + lane) * 2 + 1];
+  const float win0 = wih[(2 * H + lane) * 2], win1 = wih[(2 * H + lane) * 2 + 1];
+  const float bir = bih[lane], biz = bih[H + lane], bin = bih[2 * H + lane];
+  const float bhr = bhh[lane], bhz = bhh[H + lane], bhn = bhh[2 * H + lane];
+  const float wo0 = wout[lane], wo1 = wout[H + lane];
+  const float bo0 = bout[0], bo1 = bout[1];
+  float h = zin[(size_t)b * H + lane];
+  float x0 = 0.f, x1 = 0.f, l1 = 0.f;
+  // ---------------- forward (cil_decode_kernel's GRU roll-out) + tape ----------------
+#pragma unroll 1
+  for (int t = 0; t < T; ++t) {
+    float* rc = rec + ((size_t)b * T + t) * CIL_TRAIN_REC;
+    __builtin_amdgcn_wave_barrier();
+    a[lane] = h;
+    __builtin_amdgcn_wave_barrier();
+    float gr = bhr, gz = bhz, gn = bhn;
+#pragma unroll 16
+    for (int i = 0; i < H; ++i) {
+      const float hi = a[i];
+      gr = fmaf(wr[i], hi, gr);
+      gz = fmaf(wz[i], hi, gz);
+      gn = fmaf(wn[i], hi, gn);
+    }
+    const float ir = fmaf(wir1, x1, fmaf(wir0, x0, bir));
+    const float iz = fmaf(wiz1, x1, fmaf(wiz0, x0, biz));
+    const float in = fmaf(win1, x1, fmaf(win0, x0, bin));
+    const float r = sigmoidf_(ir + gr);
+    const float z = sigmoidf_(iz + gz);
+    const float n = tanhf_(fmaf(r, gn, in));
+    rc[REC_DGI + 0 * H + lane] = r;  // tape (lane-local; the backward overwrites these slots with dgi / dgh)
+    rc[REC_DGI + 1 * H + lane] = z;
+    rc[REC_DGI + 2 * H + lane] = n;
+    rc[REC_DGH + 0 * H + lane] = gn;
+    rc[REC_HPREV + lane] = h;
+    if (lane < 2) rc[REC_XIN + lane] = lane == 0 ? x0 : x1;
+    h = fmaf(z, h - n, n);  // (1 - z) * n + z * h
+    rc[REC_H + lane] = h;
+    const float d0 = wave_sum(wo0 * h) + bo0;
+    const float d1 = wave_sum(wo1 * h) + bo1;
+    x0 += d0;
+    x1 += d1;
+    const float* tg = target + ((size_t)b * T + t) * 2;
+    const float e0 = x0 - tg[0], e1 = x1 - tg[1];
+    l1 += fabsf(e0) + fabsf(e1);
+    rc[REC_DGH + 1 * H + lane] = signf_(e0) * inv_b;
+    rc[REC_DGH + 2 * H + lane] = signf_(e1) * inv_b;
+    if (lane == 0 && pred != nullptr) {
+      pred[((size_t)b * T + t) * 2] = x0;
+      pred[((size_t)b * T + t) * 2 + 1] = x1;
+    }
+  }
+  if (lane == 0) l1_rows[b] = l1;
+  if (!backward) return;
+  // ---------------- backward through time ----------------
+  float gx0 = 0.f, gx1 = 0.f;  // adjoint of x_t, accumulated from the later steps (wave-uniform)
+  float gh = 0.f;              // adjoint of h_t through step t+1 (lane j)
+#pragma unroll 1
+  for (int t = T - 1; t >= 0; --t) {
+    float* rc = rec + ((size_t)b * T + t) * CIL_TRAIN_REC;
+    const float r = rc[REC_DGI + 0 * H + lane], z = rc[REC_DGI + 1 * H + lane], n = rc[REC_DGI + 2 * H + lane];
+    const float ghn = rc[REC_DGH + 0 * H + lane], dp0 = rc[REC_DGH + 1 * H + lane], dp1 = rc[REC_DGH + 2 * H + lane];
+    const float hprev = rc[REC_HPREV + lane];
+    gx0 += dp0;
+    gx1 += dp1;
+    const float dh = fmaf(wo1, gx1, fmaf(wo0, gx0, gh));  // W_out^T g_x + recurrent adjoint
+    const float dn = dh * (1.0f - z);
+    const float dzg = dh * (hprev - n);
+    const float dpn = dn * (1.0f - n * n);
+    const float dghn = dpn * r;
+    const float dpr = dpn * ghn * r * (1.0f - r);
+    const float dpz = dzg * z * (1.0f - z);
+    rc[REC_DGI + 0 * H + lane] = dpr;
+    rc[REC_DGI + 1 * H + lane] = dpz;
+    rc[REC_DGI + 2 * H + lane] = dpn;
+    rc[REC_DGH + 0 * H + lane] = dpr;
+    rc[REC_DGH + 1 * H + lane] = dpz;
+    rc[REC_DGH + 2 * H + lane] = dghn;
+    if (lane < 2) rc[REC_DOUT + lane] = lane == 0 ? gx0 : gx1;
+    // into x_{t-1}, the input of this step: W_ih^T dgi (the residual part of g_x carries over unchanged)
+    gx0 += wave_sum(fmaf(win0, dpn, fmaf(wiz0, dpz, wir0 * dpr)));
+    gx1 += wave_sum(fmaf(win1, dpn, fmaf(wiz1, dpz, wir1 * dpr)));
+    // into h_{t-1}: z * dh + W_hh^T (dr, dz, dghn); lane i reads column i of W_hh
+    __builtin_amdgcn_wave_barrier();
+    a[lane] = dpr;
+    a[H + lane] = dpz;
+    a[2 * H + lane] = dghn;
+    __builtin_amdgcn_wave_barrier();
+    float s = dh * z;
+#pragma unroll 16
+    for (int j = 0; j < H; ++j) {
+      s = fmaf(ws[(0 * H + j) * WHH_LD + lane], a[j], s);
+      s = fmaf(ws[(1 * H + j) * WHH_LD + lane], a[H + j], s);
+      s = fmaf(ws[(2 * H + j) * WHH_LD + lane], a[2 * H + j], s);
+    }
+    gh = s;
+  }
+  dz[(size_t)b * H + lane] = gh;
+}
+
 }  // namespace
 
 int cil_blob_floats() { return CIL_BLOB; }
@@ -127,6 +272,15 @@ int cil_blob_floats() { return CIL_BLOB; }
 hipError_t launch_cil_decode(const float* feat, const float* vec, const float* w, int B, int T, float* y, hipStream_t s) {
   if (B <= 0 || T <= 0) return hipSuccess;
   hipLaunchKernelGGL(cil_decode_kernel, dim3((B + WAVES - 1) / WAVES), dim3(WAVES * 64), 0, s, feat, vec, w, B, T, y);
+  return hipGetLastError();
+}
+
+hipError_t launch_cil_train(const float* wih, const float* whh, const float* bih, const float* bhh, const float* wout,
+                            const float* bout, const float* z, const float* target, int B, int T, int backward,
+                            float* pred, float* l1_rows, float* dz, float* records, hipStream_t s) {
+  if (B <= 0 || T <= 0) return hipSuccess;
+  hipLaunchKernelGGL(cil_train_kernel, dim3((B + TW - 1) / TW), dim3(TW * 64), 0, s, wih, whh, bih, bhh, wout, bout, z,
+                     target, B, T, 1.0f / (float)B, backward, pred, l1_rows, dz, records);
   return hipGetLastError();
 }
 

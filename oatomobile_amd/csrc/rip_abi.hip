@@ -1002,6 +1002,7 @@ int rip_train_forward_backward(rip_trainer* t, float* params_dev, float* grads_d
                                int batch_stats, float* loss_dev, float* z_dev, rip_stream_t stream) {
   REQUIRE(t != nullptr, "trainer is NULL");
   Trainer* tr = reinterpret_cast<Trainer*>(t);
+  REQUIRE(trainer_cil_horizon(tr) == 0, "a CIL trainer (rip_cil_train_create): use rip_cil_train_forward_backward");
   REQUIRE(params_dev != nullptr && visual_dev != nullptr && vec_dev != nullptr && y_dev != nullptr && loss_dev != nullptr,
           "NULL argument");
   // any B >= 1: like torch's BatchNorm2d, batch statistics need more than one value per channel, and the smallest map
@@ -1012,6 +1013,45 @@ int rip_train_forward_backward(rip_trainer* t, float* params_dev, float* grads_d
   TraceRange range_(grads_dev != nullptr ? "rip_train_forward_backward" : "rip_train_forward");
   HIP_TRY(trainer_step(tr, params_dev, grads_dev, visual_dev, vec_dev, y_dev, dropout_mask_dev, B, batch_stats, loss_dev,
                        z_dev, (hipStream_t)stream));
+  return RIP_OK;
+}
+
+// ---------------- CIL training step (train.hip, cil.hip) ----------------
+size_t rip_cil_train_numel(int in_channels) {
+  return in_channels >= 1 && in_channels <= 16 ? cil_train_numel(in_channels) : 0;
+}
+
+int rip_cil_train_create(rip_trainer** out, int in_channels, int horizon_T, int max_batch, int device) {
+  REQUIRE(out != nullptr, "out is NULL");
+  REQUIRE(in_channels >= 1 && in_channels <= 16, "in_channels=%d outside [1,16]", in_channels);
+  REQUIRE(horizon_T >= 1 && horizon_T <= 1000, "horizon_T=%d outside [1,1000]", horizon_T);
+  REQUIRE(max_batch >= 1, "max_batch=%d must be >= 1", max_batch);
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  REQUIRE(device >= 0 && device < ndev, "device %d not in [0,%d)", device, ndev);
+  DeviceScope scope(device);
+  if (scope.err != hipSuccess) return fail(RIP_EHIP, "hipSetDevice(%d) failed: %s", device, hipGetErrorString(scope.err));
+  Trainer* t = nullptr;
+  hipError_t e = trainer_create(&t, in_channels, max_batch, device, horizon_T);
+  if (e != hipSuccess) return fail(RIP_EHIP, "trainer workspace allocation failed: %s", hipGetErrorString(e));
+  *out = reinterpret_cast<rip_trainer*>(t);
+  return RIP_OK;
+}
+
+int rip_cil_train_forward_backward(rip_trainer* t, float* params_dev, float* grads_dev, const float* visual_dev,
+                                   const float* vec_dev, const float* target_dev, const float* dropout_mask_dev, int B,
+                                   int train, float* loss_dev, float* pred_dev, rip_stream_t stream) {
+  REQUIRE(t != nullptr, "trainer is NULL");
+  Trainer* tr = reinterpret_cast<Trainer*>(t);
+  REQUIRE(trainer_cil_horizon(tr) > 0, "a DIM trainer (rip_train_create): use rip_train_forward_backward");
+  REQUIRE(params_dev != nullptr && visual_dev != nullptr && vec_dev != nullptr && target_dev != nullptr &&
+              loss_dev != nullptr, "NULL argument");
+  REQUIRE(B >= 1 && B <= trainer_max_batch(tr), "B=%d outside [1,max_batch=%d]", B, trainer_max_batch(tr));
+  DeviceScope scope(trainer_device(tr));
+  if (scope.err != hipSuccess) return fail(RIP_EHIP, "hipSetDevice failed: %s", hipGetErrorString(scope.err));
+  TraceRange range_(grads_dev != nullptr ? "rip_cil_train_forward_backward" : "rip_cil_train_forward");
+  HIP_TRY(cil_trainer_step(tr, params_dev, grads_dev, visual_dev, vec_dev, target_dev, dropout_mask_dev, B, train,
+                           loss_dev, pred_dev, (hipStream_t)stream));
   return RIP_OK;
 }
 

@@ -40,7 +40,7 @@ namespace rip {
 namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-constexpr int FEAT = 128, LAST_C = 1280, VEC = 5, HID = 64;
+constexpr int FEAT = 128, LAST_C = 1280, VEC = 5, CIL_VEC = 6, HID = 64;  // merger input: FEAT + VEC (DIM) / CIL_VEC
 // a buffer descriptor over [base, base + bytes): loads at a byte offset beyond it return zeros, with no branch
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t gemm_srd(const void* base, size_t bytes) {
   const unsigned long long p = reinterpret_cast<unsigned long long>(base);
@@ -1035,6 +1035,8 @@ __global__ __launch_bounds__(256) void colsum_segs_kernel(const float* __restric
     g.out[seg][c] = t;
   }
 }
+// *loss = -mean(q) (DIM: q = log_prob - logabsdet) or, NEG = false, mean(q) (CIL: q = the rows' L1 sums)
+template <bool NEG>
 __global__ void mean_loss_kernel(const float* __restrict__ q, float* __restrict__ loss, int B) {
   __shared__ float red[256];
   float s = 0.f;
@@ -1045,7 +1047,7 @@ __global__ void mean_loss_kernel(const float* __restrict__ q, float* __restrict_
     if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
     __syncthreads();
   }
-  if (threadIdx.x == 0) *loss = -red[0] / (float)B;  // dim/train.py:201
+  if (threadIdx.x == 0) *loss = (NEG ? -red[0] : red[0]) / (float)B;  // dim/train.py:201, cil/train.py:180
 }
 
 // torch.optim.Adam (defaults: betas (0.9, 0.999), eps 1e-8, amsgrad False), L2 weight decay added to the gradient;
@@ -1083,7 +1085,10 @@ struct Trainer {
   EncoderPlan plan;
   std::vector<TrainLayer> tl;
   size_t cls_w, cls_b, mrg_w[3], mrg_b[3];
-  size_t f_wih, f_whh, f_bih, f_bhh, f_w1, f_b1, f_w2, f_b2;
+  size_t f_wih, f_whh, f_bih, f_bhh, f_w1, f_b1, f_w2, f_b2;  // GRUCell (both models) and the DIM flow's head
+  size_t c_wo = 0, c_bo = 0;                                    // CIL: _output.weight [2,64], _output.bias [2]
+  int vec_w = VEC;  // merger input = FEAT + vec_w (5 for DIM, 6 for CIL: the extra `mode` column)
+  int cil_T = 0;    // 0: DIM; else the CIL decoder's number of steps
   size_t numel = 0;
   size_t act_per_image = 0;  // floats per image over all conv layers
   int C = 0, max_batch = 0, device = 0;
@@ -1094,13 +1099,14 @@ struct Trainer {
   float *sums = nullptr;     // per layer (sum g, sum g xhat) of the backward pass [stats_floats]
   float *partial = nullptr;  // first-stage table of the per-channel reductions (stat_grid / stat_reduce_kernel)
   float* tail = nullptr;  // pooled, feat/merged, h1, h2, z and their gradients
-  float* flowbuf = nullptr;
+  float* flowbuf = nullptr;  // decoder records: DIM flow (B rows + the relaid blob) or CIL (B * cil_T rows)
   size_t max_act = 0, stats_floats = 0, partial_floats = 0;
 };
 
 static size_t round4(size_t n) { return n; }
 
-size_t train_numel(int in_channels) {
+// encoder (conv stack + classifier) and merger floats of the packed vector, merger input FEAT + vec_w
+static size_t encoder_merger_numel(int in_channels, int vec_w) {
   const EncoderPlan plan = build_encoder_plan(in_channels);
   size_t pos = 0;
   for (const Layer& l : plan.layers) {
@@ -1108,10 +1114,18 @@ size_t train_numel(int in_channels) {
     pos += per_out * l.cout + 4 * (size_t)l.cout;
   }
   pos += (size_t)FEAT * LAST_C + FEAT;
-  const int sizes[4] = {FEAT + VEC, HID, HID, HID};
+  const int sizes[4] = {FEAT + vec_w, HID, HID, HID};
   for (int i = 0; i < 3; ++i) pos += (size_t)sizes[i + 1] * sizes[i] + sizes[i + 1];
-  pos += 192 * 2 + 192 * 64 + 192 + 192 + 32 * 64 + 32 + 4 * 32 + 4;
-  return round4(pos);
+  return pos;
+}
+
+size_t train_numel(int in_channels) {
+  return round4(encoder_merger_numel(in_channels, VEC) + 192 * 2 + 192 * 64 + 192 + 192 + 32 * 64 + 32 + 4 * 32 + 4);
+}
+
+// arch.cil_state_dict_spec minus the counters: encoder, classifier, merger (134 -> 64 -> 64 -> 64), GRUCell, _output
+size_t cil_train_numel(int in_channels) {
+  return encoder_merger_numel(in_channels, CIL_VEC) + 192 * 2 + 192 * 64 + 192 + 192 + 2 * 64 + 2;
 }
 
 // launch shape of the per-channel reduction kernels: (row chunks, 64-channel chunks), about 512 blocks in all (measured
@@ -1125,12 +1139,14 @@ static dim3 stat_grid(size_t M, int C, int* rows_per_block, int* ld) {
   return dim3(gx, (unsigned)chunks);
 }
 
-hipError_t trainer_create(Trainer** out, int in_channels, int max_batch, int device) {
+hipError_t trainer_create(Trainer** out, int in_channels, int max_batch, int device, int cil_T) {
   Trainer* t = new Trainer();
   t->plan = build_encoder_plan(in_channels);
   t->C = in_channels;
   t->max_batch = max_batch;
   t->device = device;
+  t->cil_T = cil_T;
+  t->vec_w = cil_T > 0 ? CIL_VEC : VEC;
   size_t pos = 0, act = 0, chans = 0;
   const int nl = (int)t->plan.layers.size();
   t->tl.resize(nl);
@@ -1161,7 +1177,7 @@ hipError_t trainer_create(Trainer** out, int in_channels, int max_batch, int dev
   pos += (size_t)FEAT * LAST_C;
   t->cls_b = pos;
   pos += FEAT;
-  const int sizes[4] = {FEAT + VEC, HID, HID, HID};
+  const int sizes[4] = {FEAT + t->vec_w, HID, HID, HID};
   for (int i = 0; i < 3; ++i) {
     t->mrg_w[i] = pos;
     pos += (size_t)sizes[i + 1] * sizes[i];
@@ -1176,14 +1192,21 @@ hipError_t trainer_create(Trainer** out, int in_channels, int max_batch, int dev
   pos += 192;
   t->f_bhh = pos;
   pos += 192;
-  t->f_w1 = pos;
-  pos += 32 * 64;
-  t->f_b1 = pos;
-  pos += 32;
-  t->f_w2 = pos;
-  pos += 4 * 32;
-  t->f_b2 = pos;
-  pos += 4;
+  if (cil_T > 0) {
+    t->c_wo = pos;
+    pos += 2 * 64;
+    t->c_bo = pos;
+    pos += 2;
+  } else {
+    t->f_w1 = pos;
+    pos += 32 * 64;
+    t->f_b1 = pos;
+    pos += 32;
+    t->f_w2 = pos;
+    pos += 4 * 32;
+    t->f_b2 = pos;
+    pos += 4;
+  }
   t->numel = pos;
   t->stats_floats = 2 * chans;
   hipError_t e = hipSuccess;
@@ -1205,7 +1228,10 @@ hipError_t trainer_create(Trainer** out, int in_channels, int max_batch, int dev
   }
   alloc(&t->partial, t->partial_floats);
   alloc(&t->tail, B * (size_t)TRAIN_TAIL_FLOATS);
-  alloc(&t->flowbuf, B * (size_t)FLOW_TRAIN_ROW_FLOATS + FW_SIZE);
+  if (cil_T > 0)
+    alloc(&t->flowbuf, B * (size_t)cil_T * CIL_TRAIN_REC);
+  else
+    alloc(&t->flowbuf, B * (size_t)FLOW_TRAIN_ROW_FLOATS + FW_SIZE);
   if (e != hipSuccess) {
     trainer_destroy(t);
     return e;
@@ -1225,6 +1251,7 @@ void trainer_destroy(Trainer* t) {
 size_t trainer_numel(const Trainer* t) { return t->numel; }
 int trainer_max_batch(const Trainer* t) { return t->max_batch; }
 int trainer_device(const Trainer* t) { return t->device; }
+int trainer_cil_horizon(const Trainer* t) { return t->cil_T; }
 
 // marks the trainable entries of the packed vector (everything but the BatchNorm running statistics)
 void trainer_trainable_mask(const Trainer* t, unsigned char* mask) {
@@ -1241,19 +1268,55 @@ void trainer_trainable_mask(const Trainer* t, unsigned char* mask) {
     if (e_ != hipSuccess) return e_; \
   } while (0)
 
-hipError_t trainer_step(Trainer* t, float* params, float* grads, const float* visual, const float* vec, const float* y,
-                        const float* dropout_mask, int B, int batch_stats, float* loss, float* z_out, hipStream_t s) {
-  const int nl = (int)t->plan.layers.size();
-  const size_t Bz = (size_t)B;
+// one step's arguments and the tail buffers, shared by the halves of the DIM and CIL steps
+struct StepCtx {
+  Trainer* t;
+  float* params;
+  float* grads;
+  const float* visual;
+  const float* dropout_mask;
+  int B, batch_stats;
+  hipStream_t s;
+  std::vector<size_t> stat_off;  // per conv layer: offset of its (mean, invstd) in t->stats
+  // t->tail, per batch row: pooled 1280 | merged FEAT + vec_w | h1 | h2 | z | dz | dh2 | dh1 (64 each) |
+  // dmerged FEAT + vec_w | dpooled 1280 | q 1
+  float *pooled, *merged, *h1, *h2, *zz, *dz, *dh2, *dh1, *dmerged, *dpooled, *qrow;
   // activation arenas are laid out layer-major: layer i occupies [B * act_off_i, B * act_off_i + B * a_i)
-  auto A = [&](float* base, int i) { return base + Bz * t->tl[i].act_off; };
-  const bool forward_only = grads == nullptr;  // evaluate_step: loss and z only, no gradient buffers touched
-  if (!forward_only) {
-    TRY(hipMemsetAsync(grads, 0, t->numel * sizeof(float), s));
+  float* act(float* base, int i) const { return base + (size_t)B * t->tl[i].act_off; }
+
+  StepCtx(Trainer* t_, float* params_, float* grads_, const float* visual_, const float* mask_, int B_, int bs_,
+          hipStream_t s_)
+      : t(t_), params(params_), grads(grads_), visual(visual_), dropout_mask(mask_), B(B_), batch_stats(bs_), s(s_) {
+    const size_t Bz = (size_t)B, nin = FEAT + t->vec_w;
+    pooled = t->tail;
+    merged = pooled + Bz * LAST_C;
+    h1 = merged + Bz * nin;
+    h2 = h1 + Bz * HID;
+    zz = h2 + Bz * HID;
+    dz = zz + Bz * HID;
+    dh2 = dz + Bz * HID;
+    dh1 = dh2 + Bz * HID;
+    dmerged = dh1 + Bz * HID;
+    dpooled = dmerged + Bz * nin;
+    qrow = dpooled + Bz * LAST_C;
   }
+};
+
+// encoder forward in train (batch_stats: BatchNorm batch statistics + running-stat update) or eval mode
+static hipError_t encoder_forward(StepCtx& c) {
+  Trainer* t = c.t;
+  float* params = c.params;
+  const int B = c.B;
+  const size_t Bz = (size_t)B;
+  const hipStream_t s = c.s;
+  const int nl = (int)t->plan.layers.size();
+  auto A = [&](float* base, int i) { return c.act(base, i); };
+  const float* visual = c.visual;
+  const int batch_stats = c.batch_stats;
   // ================================== forward ==================================
   size_t st_off = 0;
-  std::vector<size_t> stat_off(nl);
+  c.stat_off.assign(nl, 0);
+  std::vector<size_t>& stat_off = c.stat_off;
   for (int i = 0; i < nl; ++i) {
     const Layer& l = t->plan.layers[i];
     const TrainLayer& q = t->tl[i];
@@ -1298,61 +1361,58 @@ hipError_t trainer_step(Trainer* t, float* params, float* grads, const float* vi
     hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(nblk(total)), dim3(256), 0, s, pre, mean, invstd, params + q.gamma,
                        params + q.beta, res, post, total, l.cout, l.relu6);
   }
+  return hipSuccess;
+}
+
+// pool + dropout -> classifier -> cat(vec) -> merger (3 x Linear + ReLU) -> z (both models; vec is [B, vec_w])
+static hipError_t head_forward(StepCtx& c, const float* vec) {
+  Trainer* t = c.t;
+  float* params = c.params;
+  const int B = c.B;
+  const size_t Bz = (size_t)B;
+  const hipStream_t s = c.s;
+  const int nl = (int)t->plan.layers.size();
+  auto A = [&](float* base, int i) { return c.act(base, i); };
+  const float* dropout_mask = c.dropout_mask;
   // ---- tail: pool + dropout -> classifier -> cat(vec) -> merger (3 x Linear + ReLU) -> z ----
   const Layer& ll = t->plan.layers[nl - 1];
   const int P = ll.h_out * ll.h_out;
-  float* pooled = t->tail;                          // [B,1280]
-  float* merged = pooled + Bz * LAST_C;             // [B,133]: feat | vec
-  float* h1 = merged + Bz * (FEAT + VEC);           // [B,64]
-  float* h2 = h1 + Bz * HID;
-  float* zz = h2 + Bz * HID;
-  float* dz = zz + Bz * HID;
-  float* dh2 = dz + Bz * HID;
-  float* dh1 = dh2 + Bz * HID;
-  float* dmerged = dh1 + Bz * HID;                  // [B,133]
-  float* dpooled = dmerged + Bz * (FEAT + VEC);     // [B,1280]
-  float* qrow = dpooled + Bz * LAST_C;              // [B]
+  const int NIN = FEAT + t->vec_w;
+  float* pooled = c.pooled;
+  float* merged = c.merged;
+  float* h1 = c.h1;
+  float* h2 = c.h2;
+  float* zz = c.zz;
   hipLaunchKernelGGL(pool_drop_fwd_kernel, dim3(nblk(Bz * LAST_C)), dim3(256), 0, s, A(t->post, nl - 1), dropout_mask, pooled,
                      B, P, LAST_C);
-  TRY(gemm(false, true, pooled, LAST_C, params + t->cls_w, LAST_C, merged, FEAT + VEC, B, FEAT, LAST_C, 0, s));
-  hipLaunchKernelGGL(bias_act_kernel, dim3(nblk(Bz * FEAT)), dim3(256), 0, s, merged, FEAT + VEC, params + t->cls_b, B, FEAT, 0);
-  hipLaunchKernelGGL(copy_cols_kernel, dim3(nblk(Bz * VEC)), dim3(256), 0, s, vec, VEC, merged + FEAT, FEAT + VEC, B, VEC);
-  TRY(gemm(false, true, merged, FEAT + VEC, params + t->mrg_w[0], FEAT + VEC, h1, HID, B, HID, FEAT + VEC, 0, s));
+  TRY(gemm(false, true, pooled, LAST_C, params + t->cls_w, LAST_C, merged, NIN, B, FEAT, LAST_C, 0, s));
+  hipLaunchKernelGGL(bias_act_kernel, dim3(nblk(Bz * FEAT)), dim3(256), 0, s, merged, NIN, params + t->cls_b, B, FEAT, 0);
+  hipLaunchKernelGGL(copy_cols_kernel, dim3(nblk(Bz * t->vec_w)), dim3(256), 0, s, vec, t->vec_w, merged + FEAT, NIN, B, t->vec_w);
+  TRY(gemm(false, true, merged, NIN, params + t->mrg_w[0], NIN, h1, HID, B, HID, NIN, 0, s));
   hipLaunchKernelGGL(bias_act_kernel, dim3(nblk(Bz * HID)), dim3(256), 0, s, h1, HID, params + t->mrg_b[0], B, HID, 1);
   TRY(gemm(false, true, h1, HID, params + t->mrg_w[1], HID, h2, HID, B, HID, HID, 0, s));
   hipLaunchKernelGGL(bias_act_kernel, dim3(nblk(Bz * HID)), dim3(256), 0, s, h2, HID, params + t->mrg_b[1], B, HID, 1);
   TRY(gemm(false, true, h2, HID, params + t->mrg_w[2], HID, zz, HID, B, HID, HID, 0, s));
   hipLaunchKernelGGL(bias_act_kernel, dim3(nblk(Bz * HID)), dim3(256), 0, s, zz, HID, params + t->mrg_b[2], B, HID, 1);
-  if (z_out != nullptr) TRY(hipMemcpyAsync(z_out, zz, Bz * HID * sizeof(float), hipMemcpyDeviceToDevice, s));
-  // ---- flow: teacher-forced inverse + adjoint (cotangent -1/B per row), per-step records for the weight gradients ----
-  TRY(launch_flow_train(params + t->f_wih, params + t->f_whh, params + t->f_bih, params + t->f_bhh, params + t->f_w1,
-                        params + t->f_b1, params + t->f_w2, params + t->f_b2, zz, y, B, qrow, dz, t->flowbuf, s));
-  hipLaunchKernelGGL(mean_loss_kernel, dim3(1), dim3(256), 0, s, qrow, loss, B);
-  if (forward_only) return hipGetLastError();
-  {
-    const int R = B * 4;
-    const float* fb = t->flowbuf;  // [R][FLOW_TRAIN_REC]
-    const int ld = FLOW_TRAIN_REC;
-    // record columns: dgi 192 | dgh 192 | hprev 64 | u 2 | da1 32 | h 64 | do 4 | relu(a1) 32
-    const float *dgi = fb, *dgh = fb + 192, *hprev = fb + 384, *u = fb + 448, *da1 = fb + 450, *hh = fb + 482,
-                *dout = fb + 546, *ra1 = fb + 550;
-    TRY(gemm(true, false, dgi, ld, u, ld, grads + t->f_wih, 2, 192, 2, R, 0, s));
-    TRY(gemm(true, false, dgh, ld, hprev, ld, grads + t->f_whh, 64, 192, 64, R, 0, s));
-    TRY(gemm(true, false, da1, ld, hh, ld, grads + t->f_w1, 64, 32, 64, R, 0, s));
-    TRY(gemm(true, false, dout, ld, ra1, ld, grads + t->f_w2, 32, 4, 32, R, 0, s));
-    ColsumSegs g;
-    const float* cols[4] = {dgi, dgh, da1, dout};
-    const int ns[4] = {192, 192, 32, 4};
-    float* outs[4] = {grads + t->f_bih, grads + t->f_bhh, grads + t->f_b1, grads + t->f_b2};
-    g.blk0[0] = 0;
-    for (int i = 0; i < 4; ++i) {
-      g.col0[i] = (int)(cols[i] - fb);
-      g.n[i] = ns[i];
-      g.out[i] = outs[i];
-      g.blk0[i + 1] = g.blk0[i] + (ns[i] + 31) / 32;
-    }
-    hipLaunchKernelGGL(colsum_segs_kernel, dim3(g.blk0[4]), dim3(256), 0, s, fb, ld, R, g);
-  }
+  return hipSuccess;
+}
+
+// merger / classifier / pool backward from c.dz (the decoder's adjoint of z) into the last conv layer's gradient
+static hipError_t head_backward(StepCtx& c) {
+  Trainer* t = c.t;
+  float* params = c.params;
+  const int B = c.B;
+  const size_t Bz = (size_t)B;
+  const hipStream_t s = c.s;
+  const int nl = (int)t->plan.layers.size();
+  auto A = [&](float* base, int i) { return c.act(base, i); };
+  float* grads = c.grads;
+  const float* dropout_mask = c.dropout_mask;
+  const int NIN = FEAT + t->vec_w;
+  const Layer& ll = t->plan.layers[nl - 1];
+  const int P = ll.h_out * ll.h_out;
+  float *pooled = c.pooled, *merged = c.merged, *h1 = c.h1, *h2 = c.h2, *zz = c.zz, *dz = c.dz, *dh2 = c.dh2,
+        *dh1 = c.dh1, *dmerged = c.dmerged, *dpooled = c.dpooled;
   // ================================== backward ==================================
   // ---- merger / classifier ----
   hipLaunchKernelGGL(relu_bwd_colsum_kernel, dim3((HID + 31) / 32), dim3(256), 0, s, dz, zz, HID, grads + t->mrg_b[2], B, HID);
@@ -1362,13 +1422,29 @@ hipError_t trainer_step(Trainer* t, float* params, float* grads, const float* vi
   TRY(gemm(true, false, dh2, HID, h1, HID, grads + t->mrg_w[1], HID, HID, HID, B, 0, s));
   TRY(gemm(false, false, dh2, HID, params + t->mrg_w[1], HID, dh1, HID, B, HID, HID, 0, s));
   hipLaunchKernelGGL(relu_bwd_colsum_kernel, dim3((HID + 31) / 32), dim3(256), 0, s, dh1, h1, HID, grads + t->mrg_b[0], B, HID);
-  TRY(gemm(true, false, dh1, HID, merged, FEAT + VEC, grads + t->mrg_w[0], FEAT + VEC, HID, FEAT + VEC, B, 0, s));
-  TRY(gemm(false, false, dh1, HID, params + t->mrg_w[0], FEAT + VEC, dmerged, FEAT + VEC, B, FEAT + VEC, HID, 0, s));
-  TRY(gemm(true, false, dmerged, FEAT + VEC, pooled, LAST_C, grads + t->cls_w, LAST_C, FEAT, LAST_C, B, 0, s));
-  hipLaunchKernelGGL(colsum_kernel, dim3((FEAT + 31) / 32), dim3(256), 0, s, dmerged, FEAT + VEC, grads + t->cls_b, B, FEAT);
-  TRY(gemm(false, false, dmerged, FEAT + VEC, params + t->cls_w, LAST_C, dpooled, LAST_C, B, LAST_C, FEAT, 0, s));
+  TRY(gemm(true, false, dh1, HID, merged, NIN, grads + t->mrg_w[0], NIN, HID, NIN, B, 0, s));
+  TRY(gemm(false, false, dh1, HID, params + t->mrg_w[0], NIN, dmerged, NIN, B, NIN, HID, 0, s));
+  TRY(gemm(true, false, dmerged, NIN, pooled, LAST_C, grads + t->cls_w, LAST_C, FEAT, LAST_C, B, 0, s));
+  hipLaunchKernelGGL(colsum_kernel, dim3((FEAT + 31) / 32), dim3(256), 0, s, dmerged, NIN, grads + t->cls_b, B, FEAT);
+  TRY(gemm(false, false, dmerged, NIN, params + t->cls_w, LAST_C, dpooled, LAST_C, B, LAST_C, FEAT, 0, s));
   hipLaunchKernelGGL(pool_drop_bwd_kernel, dim3(nblk(Bz * P * LAST_C)), dim3(256), 0, s, dpooled, dropout_mask,
                      A(t->dpost, nl - 1), B, P, LAST_C);
+  return hipSuccess;
+}
+
+// conv stack backward, last layer first (weight gradients into grads, which hold zeros on entry)
+static hipError_t encoder_backward(StepCtx& c) {
+  Trainer* t = c.t;
+  float* params = c.params;
+  const int B = c.B;
+  const size_t Bz = (size_t)B;
+  const hipStream_t s = c.s;
+  const int nl = (int)t->plan.layers.size();
+  auto A = [&](float* base, int i) { return c.act(base, i); };
+  float* grads = c.grads;
+  const float* visual = c.visual;
+  const int batch_stats = c.batch_stats;
+  const std::vector<size_t>& stat_off = c.stat_off;
   // ---- conv stack, last layer first ----
   std::vector<char> res_writer(nl, 0);
   for (int i = 0; i < nl; ++i)
@@ -1440,6 +1516,99 @@ hipError_t trainer_step(Trainer* t, float* params, float* grads, const float* vi
       TRY(gemm(false, false, t->dpre, l.cout, params + q.w, l.cin, A(t->dpost, i - 1), l.cin, (int)M, l.cin, l.cout, acc_in, s));
     }
   }
+  return hipSuccess;
+}
+
+hipError_t trainer_step(Trainer* t, float* params, float* grads, const float* visual, const float* vec, const float* y,
+                        const float* dropout_mask, int B, int batch_stats, float* loss, float* z_out, hipStream_t s) {
+  StepCtx c(t, params, grads, visual, dropout_mask, B, batch_stats, s);
+  const size_t Bz = (size_t)B;
+  const bool forward_only = grads == nullptr;  // evaluate_step: loss and z only, no gradient buffers touched
+  if (!forward_only) {
+    TRY(hipMemsetAsync(grads, 0, t->numel * sizeof(float), s));
+  }
+  TRY(encoder_forward(c));
+  TRY(head_forward(c, vec));
+  float *zz = c.zz, *dz = c.dz, *qrow = c.qrow;
+  if (z_out != nullptr) TRY(hipMemcpyAsync(z_out, zz, Bz * HID * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // ---- flow: teacher-forced inverse + adjoint (cotangent -1/B per row), per-step records for the weight gradients ----
+  TRY(launch_flow_train(params + t->f_wih, params + t->f_whh, params + t->f_bih, params + t->f_bhh, params + t->f_w1,
+                        params + t->f_b1, params + t->f_w2, params + t->f_b2, zz, y, B, qrow, dz, t->flowbuf, s));
+  hipLaunchKernelGGL(mean_loss_kernel<true>, dim3(1), dim3(256), 0, s, qrow, loss, B);
+  if (forward_only) return hipGetLastError();
+  {
+    const int R = B * 4;
+    const float* fb = t->flowbuf;  // [R][FLOW_TRAIN_REC]
+    const int ld = FLOW_TRAIN_REC;
+    // record columns: dgi 192 | dgh 192 | hprev 64 | u 2 | da1 32 | h 64 | do 4 | relu(a1) 32
+    const float *dgi = fb, *dgh = fb + 192, *hprev = fb + 384, *u = fb + 448, *da1 = fb + 450, *hh = fb + 482,
+                *dout = fb + 546, *ra1 = fb + 550;
+    TRY(gemm(true, false, dgi, ld, u, ld, grads + t->f_wih, 2, 192, 2, R, 0, s));
+    TRY(gemm(true, false, dgh, ld, hprev, ld, grads + t->f_whh, 64, 192, 64, R, 0, s));
+    TRY(gemm(true, false, da1, ld, hh, ld, grads + t->f_w1, 64, 32, 64, R, 0, s));
+    TRY(gemm(true, false, dout, ld, ra1, ld, grads + t->f_w2, 32, 4, 32, R, 0, s));
+    ColsumSegs g;
+    const float* cols[4] = {dgi, dgh, da1, dout};
+    const int ns[4] = {192, 192, 32, 4};
+    float* outs[4] = {grads + t->f_bih, grads + t->f_bhh, grads + t->f_b1, grads + t->f_b2};
+    g.blk0[0] = 0;
+    for (int i = 0; i < 4; ++i) {
+      g.col0[i] = (int)(cols[i] - fb);
+      g.n[i] = ns[i];
+      g.out[i] = outs[i];
+      g.blk0[i + 1] = g.blk0[i] + (ns[i] + 31) / 32;
+    }
+    hipLaunchKernelGGL(colsum_segs_kernel, dim3(g.blk0[4]), dim3(256), 0, s, fb, ld, R, g);
+  }
+  TRY(head_backward(c));
+  TRY(encoder_backward(c));
+  return hipGetLastError();
+}
+
+// the CIL step (cil/train.py:168-190): encoder and merger as above on [B,6] vector inputs, then cil_train_kernel (GRU
+// decoder forward, L1 loss rows, backward through time into dz and the per-step records); loss = mean of the rows
+hipError_t cil_trainer_step(Trainer* t, float* params, float* grads, const float* visual, const float* vec,
+                            const float* target, const float* dropout_mask, int B, int batch_stats, float* loss,
+                            float* pred, hipStream_t s) {
+  StepCtx c(t, params, grads, visual, dropout_mask, B, batch_stats, s);
+  const bool forward_only = grads == nullptr;  // evaluate_step: loss and predictions only
+  if (!forward_only) {
+    TRY(hipMemsetAsync(grads, 0, t->numel * sizeof(float), s));
+  }
+  TRY(encoder_forward(c));
+  TRY(head_forward(c, vec));
+  TRY(launch_cil_train(params + t->f_wih, params + t->f_whh, params + t->f_bih, params + t->f_bhh, params + t->c_wo,
+                       params + t->c_bo, c.zz, target, B, t->cil_T, forward_only ? 0 : 1, pred, c.qrow, c.dz, t->flowbuf,
+                       s));
+  hipLaunchKernelGGL(mean_loss_kernel<false>, dim3(1), dim3(256), 0, s, c.qrow, loss, B);
+  if (forward_only) return hipGetLastError();
+  {
+    const int R = B * t->cil_T;
+    const float* rb = t->flowbuf;  // [R][CIL_TRAIN_REC]: dgi 192 | dgh 192 | h_prev 64 | h 64 | x_in 2 | dout 2
+    const int ld = CIL_TRAIN_REC;
+    const float *dgi = rb, *dgh = rb + 192, *hprev = rb + 384, *hh = rb + 448, *xin = rb + 512, *dout = rb + 514;
+    TRY(gemm(true, false, dgi, ld, xin, ld, grads + t->f_wih, 2, 192, 2, R, 0, s));
+    TRY(gemm(true, false, dgh, ld, hprev, ld, grads + t->f_whh, 64, 192, 64, R, 0, s));
+    TRY(gemm(true, false, dout, ld, hh, ld, grads + t->c_wo, 64, 2, 64, R, 0, s));
+    ColsumSegs g;
+    const float* cols[3] = {dgi, dgh, dout};
+    const int ns[3] = {192, 192, 2};
+    float* outs[3] = {grads + t->f_bih, grads + t->f_bhh, grads + t->c_bo};
+    g.blk0[0] = 0;
+    for (int i = 0; i < 3; ++i) {
+      g.col0[i] = (int)(cols[i] - rb);
+      g.n[i] = ns[i];
+      g.out[i] = outs[i];
+      g.blk0[i + 1] = g.blk0[i] + (ns[i] + 31) / 32;
+    }
+    g.col0[3] = 0;  // no fourth segment: it owns no block
+    g.n[3] = 0;
+    g.out[3] = nullptr;
+    g.blk0[4] = g.blk0[3];
+    hipLaunchKernelGGL(colsum_segs_kernel, dim3(g.blk0[3]), dim3(256), 0, s, rb, ld, R, g);
+  }
+  TRY(head_backward(c));
+  TRY(encoder_backward(c));
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
-"""DIM training step on MI355X — `oatomobile/baselines/torch/dim/train.py:175-213` behind the
-`rip_train_*` entry points of librip_hip.so (csrc/train.hip, csrc/flow.hip).
+"""DIM and CIL training steps on MI355X — `oatomobile/baselines/torch/dim/train.py:175-213` behind
+the `rip_train_*` entry points of librip_hip.so (csrc/train.hip, csrc/flow.hip), and
+`oatomobile/baselines/torch/cil/train.py:168-219` behind `rip_cil_train_*` (csrc/train.hip, csrc/cil.hip).
 
     trainer = DIMTrainer(model, lr=1e-3)                 # optim.Adam(model.parameters(), lr) (train.py:112-116)
     loss = trainer.train_step(batch)                     # train_step(model, optimizer, batch) (train.py:175-213)
@@ -17,6 +18,9 @@ Parameters, gradients and the Adam moments are single packed fp32 device tensors
 (`arch.packed_spec`), so data-parallel training is one `all_reduce` of `trainer.grads` between `backward()` and
 `apply()` (9.7 MB: the first bandwidth-relevant collective of this code base; only a trainer built with `group=`
 reduces, and the averaged gradient — not the local one — is what `clip=True` clips).
+
+`CILTrainer` is the same machinery for `BehaviouralModel` (cil/train.py): the same encoder and merger halves, the GRU
+decoder's backward-through-time (`cil_train_kernel`) and the L1 loss in place of the flow; no target perturbation.
 """
 
 import ctypes
@@ -27,25 +31,31 @@ import torch
 
 from oatomobile_amd import _lib
 from oatomobile_amd import arch
+from oatomobile_amd.cil import BehaviouralModel
 from oatomobile_amd.model import ImitativeModel
 
 DROPOUT_P = 0.2  # torchvision MobileNetV2.classifier[0]
 
 
-class DIMTrainer:
-  """One model, one device; owns the packed parameter / gradient / Adam-moment tensors and the HIP workspace."""
+class _PackedTrainer:
+  """What the DIM and CIL trainers share: one model, one device; the packed parameter / gradient / Adam-moment tensors
+  in the model's state_dict order (`_state_dict_spec` minus the `num_batches_tracked` counters), the HIP workspace
+  handle, and the step after `loss.backward()`: [all-reduce ->] [clip ->] Adam.  A subclass sets `_state_dict_spec`,
+  creates the handle in `_create` and implements `backward`."""
 
-  def __init__(self, model: ImitativeModel, lr: float = 1e-3, weight_decay: float = 0.0, noise_level: float = 1e-2,
-               max_batch: int = 512, device: Optional[torch.device] = None, betas=(0.9, 0.999), eps: float = 1e-8,
-               group=None) -> None:
+  _state_dict_spec = None  # in_channels -> ordered [(key, shape)] of the model's state_dict
+
+  def __init__(self, model, lr: float, weight_decay: float, max_batch: int, device: Optional[torch.device], betas,
+               eps: float, group) -> None:
+    name = type(self).__name__
     if not torch.cuda.is_available():
-      raise RuntimeError("oatomobile_amd.DIMTrainer needs a ROCm device; there is no CPU path.")
+      raise RuntimeError("oatomobile_amd.%s needs a ROCm device; there is no CPU path." % name)
     self._device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if self._device.index is None:
       self._device = torch.device("cuda", torch.cuda.current_device())
     self._model = model
     self._C = model._in_channels
-    self._lr, self._wd, self._noise = float(lr), float(weight_decay), float(noise_level)
+    self._lr, self._wd = float(lr), float(weight_decay)
     self._betas, self._eps = (float(betas[0]), float(betas[1])), float(eps)
     self._group = group
     if group is None and torch.distributed.is_available() and torch.distributed.is_initialized() \
@@ -53,65 +63,61 @@ class DIMTrainer:
       # torch's convention is group=None == the default WORLD group; here None means "do not reduce" (ranks that train
       # independent ensemble members).  Say so once instead of silently training unsynchronised replicas.
       import warnings
-      warnings.warn("DIMTrainer(group=None) in a %d-rank job: gradients are NOT all-reduced (independent replicas).  "
+      warnings.warn("%s(group=None) in a %d-rank job: gradients are NOT all-reduced (independent replicas).  "
                     "Pass group=torch.distributed.group.WORLD for data-parallel training." %
-                    torch.distributed.get_world_size(), stacklevel=2)
+                    (name, torch.distributed.get_world_size()), stacklevel=3)
     self._max_batch = int(max_batch)
     self._lib = _lib.load()
-    n = int(self._lib.rip_train_numel(self._C))
-    if n != arch.packed_numel(self._C):
-      raise RuntimeError("packed layout mismatch: library %d, arch.packed_spec %d" % (n, arch.packed_numel(self._C)))
     self._h = ctypes.c_void_p(0)
-    _lib.check(self._lib.rip_train_create(ctypes.byref(self._h), self._C, self._max_batch, self._device.index))
+    n = self._create()
+    spec_n = sum(int(np.prod(s)) if len(s) else 1 for _, s in self._packed_spec())
+    if n != spec_n:
+      raise RuntimeError("packed layout mismatch: library %d, state_dict spec %d" % (n, spec_n))
     mask = np.empty(n, np.uint8)
     _lib.check(self._lib.rip_train_trainable_mask(self._h, mask.ctypes.data_as(ctypes.c_void_p), n))
-    self.params = torch.from_numpy(model.packed_weights()).to(self._device)
+    self.params = torch.from_numpy(self._packed_weights(model)).to(self._device)
     self.grads = torch.zeros_like(self.params)
     self.exp_avg = torch.zeros_like(self.params)
     self.exp_avg_sq = torch.zeros_like(self.params)
     self._trainable = torch.from_numpy(mask).to(self._device)
     self._loss = torch.zeros((), device=self._device)
+    self._last_batch = 0
     self.step_count = 0
     nbt = [v for k, v in model.state_dict().items() if k.endswith("num_batches_tracked")]
     self.num_batches_tracked = int(nbt[0]) if nbt else 0  # nn.BatchNorm2d counts its train-mode forward passes
 
-  # ---- the reference's train_step, in its two halves ----
-  def backward(self, batch: Mapping[str, torch.Tensor], *, y: Optional[torch.Tensor] = None,
-               dropout_mask: Optional[torch.Tensor] = None, train: bool = True, gradients: bool = True) -> torch.Tensor:
-    """train.py:181-204: perturbs the target, runs the forward pass in train mode and back-propagates
-    `-mean(log_prob - logabsdet)`; gradients land in `self.grads`.  Returns the loss (device scalar).
-    `train=False`: running statistics, no dropout, no perturbation ("frozen" BatchNorm); `gradients=False`: forward
-    only — loss and `self.z`, `self.grads` is left alone (`evaluate_step`)."""
+  def _create(self) -> int:
+    """Creates `self._h`; returns the library's packed numel."""
+    raise NotImplementedError
+
+  def _packed_spec(self):
+    return [(k, s) for (k, s) in type(self)._state_dict_spec(self._C) if not k.endswith("num_batches_tracked")]
+
+  def _packed_weights(self, model) -> np.ndarray:
+    sd = model.state_dict()
+    return np.concatenate([sd[k].detach().cpu().numpy().astype(np.float32).reshape(-1) for k, _ in self._packed_spec()])
+
+  def _visual(self, batch: Mapping[str, torch.Tensor]) -> torch.Tensor:
+    """`visual_features` as fp32 contiguous [B,C,100,100] on the device, B <= max_batch."""
     vis = batch["visual_features"]
     if not vis.is_cuda:
-      raise RuntimeError("oatomobile_amd.DIMTrainer: the batch is on %s — no CPU path" % (vis.device,))
+      raise RuntimeError("oatomobile_amd.%s: the batch is on %s — no CPU path" % (type(self).__name__, vis.device))
     vis = vis.detach().to(torch.float32).contiguous()
-    B = vis.shape[0]
     _lib.expect_shape(vis, (None, self._C, arch.INPUT_HW, arch.INPUT_HW), "visual_features")
-    if B > self._max_batch:
-      raise ValueError("batch of %d exceeds max_batch=%d" % (B, self._max_batch))
-    vec = torch.cat([batch["velocity"].reshape(B, 3), batch["is_at_traffic_light"].reshape(B, 1),
-                     batch["traffic_light_state"].reshape(B, 1)], dim=-1).to(torch.float32).contiguous()
-    target = batch["player_future"][..., :2].to(torch.float32)
-    _lib.expect_shape(target, (B, arch.T, 2), "player_future[..., :2]")
-    if y is None:
-      y = torch.normal(mean=target, std=float(self._noise)) if train else target  # train.py:184-189 (one launch)
-    y = y.to(self._device, torch.float32).contiguous()
+    if vis.shape[0] > self._max_batch:
+      raise ValueError("batch of %d exceeds max_batch=%d" % (vis.shape[0], self._max_batch))
+    return vis
+
+  def _dropout_mask(self, B: int, train: bool, dropout_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     if train and dropout_mask is None:
       # keep with probability 1 - p, scaled by 1 / (1 - p) (nn.Dropout): two launches
       dropout_mask = torch.empty(B, arch.LAST_CHANNELS, device=self._device).bernoulli_(1.0 - DROPOUT_P).mul_(1.0 / (1.0 - DROPOUT_P))
     if dropout_mask is not None:
       dropout_mask = dropout_mask.to(self._device, torch.float32).contiguous()
       _lib.expect_shape(dropout_mask, (B, arch.LAST_CHANNELS), "dropout_mask")
-    self.z = torch.empty(B, arch.HIDDEN_SIZE, device=self._device)
-    _lib.check(self._lib.rip_train_forward_backward(
-        self._h, _lib.ptr(self.params), _lib.ptr(self.grads if gradients else None), _lib.ptr(vis), _lib.ptr(vec), _lib.ptr(y),
-        _lib.ptr(dropout_mask), B, int(train), _lib.ptr(self._loss.view(1)), _lib.ptr(self.z),
-        _lib.current_stream(self._device)))
-    if train:
-      self.num_batches_tracked += 1
-    return self._loss.clone()
+    return dropout_mask
 
+  # ---- after loss.backward(): the optimizer half of the reference's train_step ----
   def allreduce(self) -> None:
     """Data-parallel exchange: averages the packed gradient vector over the ranks of the `group` this trainer was
     built with (DistributedDataParallel semantics; BatchNorm running statistics stay per-rank buffers, there is no
@@ -145,22 +151,11 @@ class DIMTrainer:
         _lib.ptr(self._trainable, torch.uint8), self.params.numel(), self.step_count, self._lr, self._betas[0],
         self._betas[1], self._eps, self._wd, _lib.current_stream(self._device)))
 
-  def train_step(self, batch: Mapping[str, torch.Tensor], *, y: Optional[torch.Tensor] = None,
-                 dropout_mask: Optional[torch.Tensor] = None, clip: bool = False) -> torch.Tensor:
-    """train.py:175-213."""
-    loss = self.backward(batch, y=y, dropout_mask=dropout_mask)
-    self.apply(clip=clip)
-    return loss
-
-  def evaluate_step(self, batch: Mapping[str, torch.Tensor]) -> torch.Tensor:
-    """train.py:229-249 (model.eval(): running statistics, no dropout, the unperturbed target)."""
-    return self.backward(batch, train=False, gradients=False)
-
   def peek(self, layer: int, what: str = "post") -> torch.Tensor:
     """What the last `backward` saved for conv layer `layer` (0 = features.0, ...), as NCHW: "pre" (conv output
     before BatchNorm), "post" (after BatchNorm / ReLU6 / residual) or "grad" (dLoss/dpost)."""
     spec = arch.conv_layers(self._C)[layer]
-    B = self.z.shape[0]
+    B = self._last_batch
     buf = torch.empty(B, spec.h_out, spec.h_out, spec.cout, device=self._device)
     _lib.check(self._lib.rip_train_peek(self._h, layer, {"pre": 0, "post": 1, "grad": 2}[what], B, _lib.ptr(buf), buf.numel(),
                                         _lib.current_stream(self._device)))
@@ -169,7 +164,7 @@ class DIMTrainer:
   # ---- views of the packed vectors in the reference's state_dict terms ----
   def _unpack(self, vector: torch.Tensor):
     out, pos = {}, 0
-    for key, shape in arch.packed_spec(self._C):
+    for key, shape in self._packed_spec():
       n = int(np.prod(shape)) if len(shape) else 1
       out[key] = vector[pos:pos + n].view(*shape)
       pos += n
@@ -184,16 +179,16 @@ class DIMTrainer:
     the number of train-mode forward passes, like nn.BatchNorm2d keeps them)."""
     sd = self._unpack(self.params)
     full = {}
-    for key, _ in arch.state_dict_spec(self._C):
+    for key, _ in type(self)._state_dict_spec(self._C):
       if key.endswith("num_batches_tracked"):
         full[key] = torch.tensor(self.num_batches_tracked, dtype=torch.long)
       else:
         full[key] = sd[key].detach().clone()
     return full
 
-  def sync_to_model(self) -> ImitativeModel:
-    """Writes the trained weights into the wrapped `ImitativeModel` (its inference handle and every agent holding
-    the model re-upload on their next call)."""
+  def sync_to_model(self):
+    """Writes the trained weights into the wrapped model (its inference handle and every agent holding the model
+    re-upload on their next call)."""
     self._model.load_state_dict({k: v.to(self._model.device) for k, v in self.state_dict().items()}, strict=True)
     return self._model
 
@@ -207,3 +202,136 @@ class DIMTrainer:
       self.close()
     except Exception:  # interpreter shutdown
       pass
+
+
+class DIMTrainer(_PackedTrainer):
+  """One model, one device; owns the packed parameter / gradient / Adam-moment tensors and the HIP workspace."""
+
+  _state_dict_spec = staticmethod(arch.state_dict_spec)
+
+  def __init__(self, model: ImitativeModel, lr: float = 1e-3, weight_decay: float = 0.0, noise_level: float = 1e-2,
+               max_batch: int = 512, device: Optional[torch.device] = None, betas=(0.9, 0.999), eps: float = 1e-8,
+               group=None) -> None:
+    self._noise = float(noise_level)
+    super().__init__(model, lr, weight_decay, max_batch, device, betas, eps, group)
+
+  def _create(self) -> int:
+    _lib.check(self._lib.rip_train_create(ctypes.byref(self._h), self._C, self._max_batch, self._device.index))
+    return int(self._lib.rip_train_numel(self._C))
+
+  def _packed_weights(self, model) -> np.ndarray:
+    return model.packed_weights()
+
+  # ---- the reference's train_step, in its two halves ----
+  def backward(self, batch: Mapping[str, torch.Tensor], *, y: Optional[torch.Tensor] = None,
+               dropout_mask: Optional[torch.Tensor] = None, train: bool = True, gradients: bool = True) -> torch.Tensor:
+    """train.py:181-204: perturbs the target, runs the forward pass in train mode and back-propagates
+    `-mean(log_prob - logabsdet)`; gradients land in `self.grads`.  Returns the loss (device scalar).
+    `train=False`: running statistics, no dropout, no perturbation ("frozen" BatchNorm); `gradients=False`: forward
+    only — loss and `self.z`, `self.grads` is left alone (`evaluate_step`)."""
+    vis = self._visual(batch)
+    B = vis.shape[0]
+    vec = torch.cat([batch["velocity"].reshape(B, 3), batch["is_at_traffic_light"].reshape(B, 1),
+                     batch["traffic_light_state"].reshape(B, 1)], dim=-1).to(torch.float32).contiguous()
+    target = batch["player_future"][..., :2].to(torch.float32)
+    _lib.expect_shape(target, (B, arch.T, 2), "player_future[..., :2]")
+    if y is None:
+      y = torch.normal(mean=target, std=float(self._noise)) if train else target  # train.py:184-189 (one launch)
+    y = y.to(self._device, torch.float32).contiguous()
+    dropout_mask = self._dropout_mask(B, train, dropout_mask)
+    self.z = torch.empty(B, arch.HIDDEN_SIZE, device=self._device)
+    self._last_batch = B
+    _lib.check(self._lib.rip_train_forward_backward(
+        self._h, _lib.ptr(self.params), _lib.ptr(self.grads if gradients else None), _lib.ptr(vis), _lib.ptr(vec), _lib.ptr(y),
+        _lib.ptr(dropout_mask), B, int(train), _lib.ptr(self._loss.view(1)), _lib.ptr(self.z),
+        _lib.current_stream(self._device)))
+    if train:
+      self.num_batches_tracked += 1
+    return self._loss.clone()
+
+  def train_step(self, batch: Mapping[str, torch.Tensor], *, y: Optional[torch.Tensor] = None,
+                 dropout_mask: Optional[torch.Tensor] = None, clip: bool = False) -> torch.Tensor:
+    """train.py:175-213."""
+    loss = self.backward(batch, y=y, dropout_mask=dropout_mask)
+    self.apply(clip=clip)
+    return loss
+
+  def evaluate_step(self, batch: Mapping[str, torch.Tensor]) -> torch.Tensor:
+    """train.py:229-249 (model.eval(): running statistics, no dropout, the unperturbed target)."""
+    return self.backward(batch, train=False, gradients=False)
+
+  def sync_to_model(self) -> ImitativeModel:
+    """Writes the trained weights into the wrapped `ImitativeModel` (its inference handle and every agent holding
+    the model re-upload on their next call)."""
+    return super().sync_to_model()
+
+
+class CILTrainer(_PackedTrainer):
+  """The behavioural-cloning step of oatomobile/baselines/torch/cil/train.py on one `BehaviouralModel`, one device:
+
+      trainer = CILTrainer(model, lr=1e-3, weight_decay=0.0)   # optim.Adam(params, lr, weight_decay) (train.py:113-118)
+      loss = trainer.train_step(batch, clip=False)              # train_step (train.py:168-190)
+      loss = trainer.evaluate_step(batch)                       # evaluate_step (train.py:208-219)
+      trainer.sync_to_model()                                   # the weights back into `model` (and its CILAgent)
+
+  `batch` is what `BehaviouralModel.transform` produces (cil/model.py:129-170), on the device: `visual_features
+  [B,C,100,100]`, `velocity [B,3]`, `is_at_traffic_light [B,1]`, `traffic_light_state [B,1]`, `mode [B,1]` and
+  `player_future [B,T,>=2]`, T = `model._output_shape[0]` (the reference trains with T = 4).  Loss:
+  `mean_b sum_{t,d} |predictions - player_future[..., :2]|` (nn.L1Loss(reduction="none") summed over [-2, -1]).
+  Train mode: BatchNorm batch statistics (running statistics updated), Dropout(0.2) before the classifier — the only
+  random draw (there is no target perturbation); `dropout_mask=` replays one."""
+
+  _state_dict_spec = staticmethod(arch.cil_state_dict_spec)
+
+  def __init__(self, model: BehaviouralModel, lr: float = 1e-3, weight_decay: float = 0.0, max_batch: int = 512,
+               device: Optional[torch.device] = None, betas=(0.9, 0.999), eps: float = 1e-8, group=None) -> None:
+    self._T = int(model._output_shape[0])
+    super().__init__(model, lr, weight_decay, max_batch, device, betas, eps, group)
+    self.predictions = None
+
+  def _create(self) -> int:
+    _lib.check(self._lib.rip_cil_train_create(ctypes.byref(self._h), self._C, self._T, self._max_batch,
+                                              self._device.index))
+    return int(self._lib.rip_cil_train_numel(self._C))
+
+  def backward(self, batch: Mapping[str, torch.Tensor], *, dropout_mask: Optional[torch.Tensor] = None,
+               train: bool = True, gradients: bool = True) -> torch.Tensor:
+    """cil/train.py:176-183: forward in train mode, the L1 loss and its backward; gradients land in `self.grads`, the
+    predictions [B,T,2] in `self.predictions`.  Returns the loss (device scalar).  `train=False`: running statistics,
+    no dropout; `gradients=False`: forward only (`evaluate_step`), `self.grads` is left alone."""
+    for key in ("visual_features", "velocity", "is_at_traffic_light", "traffic_light_state", "mode", "player_future"):
+      if key not in batch:
+        raise ValueError("Missing `%s` in the batch." % key)
+    vis = self._visual(batch)
+    B = vis.shape[0]
+    vec = torch.cat([batch["velocity"].reshape(B, 3), batch["is_at_traffic_light"].reshape(B, 1),
+                     batch["traffic_light_state"].reshape(B, 1), batch["mode"].reshape(B, 1)],
+                    dim=-1).to(self._device, torch.float32).contiguous()  # cil/model.py:88-98
+    target = batch["player_future"][..., :2].to(self._device, torch.float32).contiguous()
+    _lib.expect_shape(target, (B, self._T, 2), "player_future[..., :2]")
+    dropout_mask = self._dropout_mask(B, train, dropout_mask)
+    self.predictions = torch.empty(B, self._T, 2, device=self._device)
+    self._last_batch = B
+    _lib.check(self._lib.rip_cil_train_forward_backward(
+        self._h, _lib.ptr(self.params), _lib.ptr(self.grads if gradients else None), _lib.ptr(vis), _lib.ptr(vec),
+        _lib.ptr(target), _lib.ptr(dropout_mask), B, int(train), _lib.ptr(self._loss.view(1)),
+        _lib.ptr(self.predictions), _lib.current_stream(self._device)))
+    if train:
+      self.num_batches_tracked += 1
+    return self._loss.clone()
+
+  def train_step(self, batch: Mapping[str, torch.Tensor], *, dropout_mask: Optional[torch.Tensor] = None,
+                 clip: bool = False) -> torch.Tensor:
+    """cil/train.py:168-190: zero_grad, forward, L1 loss, backward, [clip_grad_norm(1.0)], Adam step."""
+    loss = self.backward(batch, dropout_mask=dropout_mask)
+    self.apply(clip=clip)
+    return loss
+
+  def evaluate_step(self, batch: Mapping[str, torch.Tensor]) -> torch.Tensor:
+    """cil/train.py:208-219 (model.eval(): running statistics, no dropout); predictions in `self.predictions`."""
+    return self.backward(batch, train=False, gradients=False)
+
+  def sync_to_model(self) -> BehaviouralModel:
+    """Writes the trained weights into the wrapped `BehaviouralModel`: its next `forward` (and every `CILAgent`
+    holding it) runs on them."""
+    return super().sync_to_model()

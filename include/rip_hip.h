@@ -27,7 +27,8 @@
  *   - a handle is bound to one device: every entry point that takes a handle
  *     makes that device current for the duration of the call and restores the
  *     caller's current device before returning.  The stateless entry points
- *     (rip_transform, rip_goal_likelihood, rip_lidar_bev, rip_cil_decode) launch
+ *     (rip_transform, rip_goal_likelihood, rip_lidar_bev, rip_cil_decode,
+ *     rip_gather_batch_u8) launch
  *     on the caller's current device, which must own the pointers.
  *   - a handle's scratch is shared by its calls, so a handle is single-stream
  *     and not thread-safe: when consecutive calls on one handle name different
@@ -313,6 +314,21 @@ int rip_cil_train_create(rip_trainer** out, int in_channels, int horizon_T, int 
 int rip_cil_train_forward_backward(rip_trainer* t, float* params_dev, float* grads_dev, const float* visual_dev,
                                    const float* vec_dev, const float* target_dev, const float* dropout_mask_dev, int B,
                                    int train, float* loss_dev, float* pred_dev, rip_stream_t stream);
+
+/* A trainer batch out of a device-resident coded cache (oatomobile_amd/replay.py: DeviceCache.batch), one launch:
+ * rows_dev [B] int64 row indices (repeats allowed) into codes_dev [n,H,W,C] uint8 / lut_dev [256] (the packed replay
+ * cache, as rip_encode_raw_u8), vec_dev [n,5], future_dev [n,L,2] and mode_dev [n] (may be NULL) ->
+ *   visual_dev [B,C,out_hw,out_hw]  = rip_transform(lut[codes[rows]], channels_last=1), bit for bit,
+ *   vec_out_dev [B,5]               = vec[rows],
+ *   target_dev [B,T,2]              = future[rows, 0::stride, :] (transforms.downsample_target; the caller checks that
+ *                                     the slice has T steps: (L + stride - 1) / stride == T),
+ *   mode_out_dev [B] (may be NULL; needs mode_dev) = mode[rows] with STOP (1) -> FORWARD (0) (cil/model.py:166-168).
+ * Offsets are 64-bit.  A row outside [0, n) reads nothing and yields NaN outputs for that row.  C <= 4 and a
+ * down-sampling factor <= 2.  Stateless: launches on the caller's current device. */
+int rip_gather_batch_u8(const uint8_t* codes_dev, const float* lut_dev, const int64_t* rows_dev, int B, int64_t n, int C,
+                        int H, int W, int out_hw, const float* vec_dev, const float* future_dev, int L, int T, int stride,
+                        const float* mode_dev, float* visual_dev, float* vec_out_dev, float* target_dev,
+                        float* mode_out_dev, rip_stream_t stream);
 
 /* Implementation knobs (results are identical within the parity tolerance; tests run every setting).
  *   RIP_OPT_SEARCH_KERNEL: 0 = auto (the split-f16 phase-sequential kernel when B*N >= 1280 and N % 16 == 0, else

@@ -33,13 +33,17 @@ def load_datum(fname: str, modalities: Sequence[str] = MODALITIES, mode: bool = 
         v = np.transpose(v, (2, 0, 1))
       sample[attr] = v
   if mode and "player_future" in sample:
-    x_T, y_T = sample["player_future"][-1, :2]
-    norm = np.linalg.norm([x_T, y_T])
-    theta = np.degrees(np.arccos(x_T / (norm + 1e-3)))
-    label = 1 if norm < 3 else (2 if theta > 15 else (3 if theta <= -15 else 0))
-    sample["mode"] = np.atleast_1d(label).astype(np.float32)
+    sample["mode"] = np.atleast_1d(mode_label(sample["player_future"])).astype(np.float32)
   sample["name"] = fname
   return sample
+
+
+def mode_label(player_future: np.ndarray) -> int:
+  """datasets/carla.py:148-162: the driving-mode label of a datum from its last future waypoint."""
+  x_T, y_T = player_future[-1, :2]
+  norm = np.linalg.norm([x_T, y_T])
+  theta = np.degrees(np.arccos(x_T / (norm + 1e-3)))
+  return 1 if norm < 3 else (2 if theta > 15 else (3 if theta <= -15 else 0))
 
 
 def goal_from_future(player_future: np.ndarray, num_goals: int = 10, stride: int = 8) -> np.ndarray:
@@ -50,8 +54,9 @@ def goal_from_future(player_future: np.ndarray, num_goals: int = 10, stride: int
   return g
 
 
-def _fill_rows(files, j0, lidar, vec, goal, num_goals, goal_stride):
-  """Decodes `files` into rows j0.. of the batch arrays (numpy views; shared memory in the worker processes)."""
+def _fill_rows(files, j0, lidar, vec, goal, num_goals, goal_stride, future=None, mode=None):
+  """Decodes `files` into rows j0.. of the batch arrays (numpy views; shared memory in the worker processes); with
+  `future` / `mode` also the training targets `player_future[:, :2]` and `load_datum(mode=True)`'s label."""
   for j, f in enumerate(files, start=j0):
     d = load_datum(f)
     lidar[j] = d["lidar"]
@@ -59,6 +64,9 @@ def _fill_rows(files, j0, lidar, vec, goal, num_goals, goal_stride):
     vec[j, 3] = float(d["is_at_traffic_light"].reshape(-1)[0])
     vec[j, 4] = float(d["traffic_light_state"].reshape(-1)[0])
     goal[j] = goal_from_future(d["player_future"], num_goals, goal_stride)
+    if future is not None:
+      future[j] = d["player_future"][:, :2]
+      mode[j] = mode_label(d["player_future"])
   return len(files)
 
 
@@ -86,17 +94,20 @@ def code_bev(bits: np.ndarray, table: np.ndarray):
   return c.astype(np.uint8).reshape(bits.shape), table
 
 
-def pack_span(files, i0, out_dir, shape, num_goals, goal_stride, chunk):
+def pack_span(files, i0, out_dir, shape, num_goals, goal_stride, chunk, future_len=0):
   """Packs `files` into rows i0.. of `<out_dir>/codes.npy` (an existing memmap of `shape`), one datum at a time through
   a reused frame buffer (a chunk-sized float32 staging array costs more in first-touch page faults than the decode),
   coded against the table of THIS span as known so far; when a datum brings a new value the rows of the current chunk
-  are re-coded at once, so every chunk is consistent with one table.  Returns [(row0, rows, that table)], vec, goal:
-  the parent unifies the tables and re-codes the chunks whose table differs from the final one."""
+  are re-coded at once, so every chunk is consistent with one table.  Returns [(row0, rows, that table)], vec, goal,
+  future, mode: the parent unifies the tables and re-codes the chunks whose table differs from the final one.
+  `future_len` > 0: also the training targets, future [m, future_len, 2] and mode [m] (else both None)."""
   n, H, W, C = shape
   codes = np.lib.format.open_memmap(os.path.join(out_dir, "codes.npy"), mode="r+")
   assert codes.shape == tuple(shape) and codes.dtype == np.uint8
   vec = np.empty((len(files), 5), np.float32)
   goal = np.empty((len(files), num_goals, 2), np.float32)
+  future = np.empty((len(files), future_len, 2), np.float32) if future_len else None
+  mode = np.empty((len(files),), np.float32) if future_len else None
   table = np.empty((0,), np.uint32)
   frame = np.empty((1, H, W, C), np.float32)
   bits = frame.view(np.uint32)
@@ -104,7 +115,8 @@ def pack_span(files, i0, out_dir, shape, num_goals, goal_stride, chunk):
   for j0 in range(0, len(files), chunk):
     part = files[j0:j0 + chunk]
     for j, f in enumerate(part, start=j0):
-      _fill_rows([f], 0, frame, vec[j:j + 1], goal[j:j + 1], num_goals, goal_stride)
+      _fill_rows([f], 0, frame, vec[j:j + 1], goal[j:j + 1], num_goals, goal_stride,
+                 None if future is None else future[j:j + 1], None if mode is None else mode[j:j + 1])
       c, grown = code_bev(bits, table)
       if grown.size != table.size and j > j0:  # a new value inside the chunk: its earlier rows move to the new table
         remap = np.searchsorted(grown, table).astype(np.uint8)
@@ -114,18 +126,19 @@ def pack_span(files, i0, out_dir, shape, num_goals, goal_stride, chunk):
     spans.append((i0 + j0, len(part), table.copy()))
   codes.flush()
   del codes
-  return spans, vec, goal
+  return spans, vec, goal, future, mode
 
 
 if __name__ == "__main__":  # worker process of replay.pack_cache: `python _datum.py job.json` -> job["result"] (.npz)
   with open(sys.argv[1]) as fh:
     job = json.load(fh)
   try:
-    spans, vec, goal = pack_span(job["files"], job["i0"], job["out_dir"], tuple(job["shape"]), job["num_goals"],
-                                 job["goal_stride"], job["chunk"])
+    spans, vec, goal, future, mode = pack_span(job["files"], job["i0"], job["out_dir"], tuple(job["shape"]),
+                                               job["num_goals"], job["goal_stride"], job["chunk"], job.get("future_len", 0))
+    targets = {} if future is None else dict(future=future, mode=mode)
     np.savez(job["result"], vec=vec, goal=goal, rows=np.array([(a, b) for a, b, _ in spans], np.int64),
              sizes=np.array([t.size for _, _, t in spans], np.int64),
-             tables=np.concatenate([t for _, _, t in spans]) if spans else np.empty((0,), np.uint32))
+             tables=np.concatenate([t for _, _, t in spans]) if spans else np.empty((0,), np.uint32), **targets)
   except ValueError as exc:  # refused data (NaN, > 256 values): the parent re-raises it as ValueError
     with open(job["result"] + ".err", "w") as fh:
       fh.write(str(exc))

@@ -81,6 +81,10 @@ SIGNATURES = [
     ("rip_cil_train_create", c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     ("rip_cil_train_forward_backward", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("rip_gather_batch_u8", c_int, [
+        c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p
+    ]),
 ]
 ABI_VERSION = 4
 

@@ -126,6 +126,14 @@ hipError_t launch_transform_coded(const uint8_t* in, const float* lut /*[256]*/,
                                   float* out, hipStream_t s);
 hipError_t launch_transform(const float* in, int B, int C, int H, int W, int channels_last, int out_hw, float* out,
                             hipStream_t s);
+// replay.DeviceCache batches: rows [B] int64 of a coded cache (codes [n,H,W,C] uint8, lut [256], vec [n,5], future
+// [n,L,2], mode [n] or NULL) -> visual [B,C,out_hw,out_hw], vec_out [B,5], target [B,T,2] = future[rows, 0::stride][:T],
+// mode_out [B] (STOP -> FORWARD) or NULL.  C <= 4.
+bool gather_batch_supported(int C, int H, int W, int out_hw);
+hipError_t launch_gather_batch(const uint8_t* codes, const float* lut, const int64_t* rows, int B, int64_t n, int C, int H,
+                               int W, int out_hw, const float* vec, const float* future, int L, int T, int stride,
+                               const float* mode, float* visual, float* vec_out, float* target, float* mode_out,
+                               hipStream_t s);
 
 // Runs the encoder + merger for models [k0, k0+kc) on B observations.
 //   enc_w: [K_total][plan.blob_floats]; visual [B,C,100,100]; vec [B,5]; bufs[4]: each >= kc*B*max_act floats.

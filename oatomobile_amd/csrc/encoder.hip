@@ -75,9 +75,11 @@ constexpr int TR_P = 2 * TR_T + 4;  // input patch edge bound for scale <= 2.02 
 // TIN = float: the sensor's float32 BEV.  TIN = uint8_t: a CODED BEV (replay cache, oatomobile_amd/replay.py): every
 // cell holds an index into `lut` (256 float32 values, the distinct values of the float BEV it was packed from), looked
 // up while the patch is staged — a quarter of the bytes, the same float32 values, hence bit-identical outputs.
-template <int C, bool CL, typename TIN = float>
-__global__ __launch_bounds__(256) void transform_kernel(const TIN* __restrict__ in, const float* __restrict__ lut, int H,
-                                                         int W, int O, float* __restrict__ out) {
+// One TxT output tile (ti, tj) of ONE image: `in` points at the image, `out` at its [C,O,O] output, `patch` at the
+// dynamic LDS (patch, then for TIN = uint8_t the 256-entry table).  Called by transform_kernel and gather_batch_kernel.
+template <int C, bool CL, typename TIN>
+__device__ __forceinline__ void transform_tile(const TIN* __restrict__ in, const float* __restrict__ lut, int H, int W,
+                                               int O, float* __restrict__ out, int ti, int tj, float* patch) {
   // The patch keeps the memory order of the input; all staging loads of a thread are issued before the first LDS
   // write (the kernel is pure latency otherwise), and the row pitch is odd so the interpolation reads (consecutive
   // lanes sit two patch rows apart) spread over the banks.
@@ -86,13 +88,12 @@ __global__ __launch_bounds__(256) void transform_kernel(const TIN* __restrict__ 
   constexpr int PITCH = ROW + 1;
   constexpr int TOTAL = ROW * NROWS;
   constexpr int ITER = (TOTAL + 255) / 256;
-  extern __shared__ float patch[];
   constexpr bool CODED = sizeof(TIN) == 1;
   float* lut_s = patch + PITCH * NROWS;  // CODED: the table, behind the patch
   if (CODED) lut_s[threadIdx.x] = lut[threadIdx.x];
   const float sh = O > 1 ? (float)(H - 1) / (float)(O - 1) : 0.f;
   const float sw = O > 1 ? (float)(W - 1) / (float)(O - 1) : 0.f;
-  const int b = blockIdx.z, ti = blockIdx.y, tj = blockIdx.x;  // ti: output rows i (input x), tj: output cols j (input y)
+  // ti: output rows i (input x), tj: output cols j (input y)
   const int i0 = ti * TR_T, j0 = tj * TR_T;
   const int y0 = (int)(sh * (float)j0), x0 = (int)(sw * (float)i0);
   const int py = min(TR_P, H - y0), px = min(TR_P, W - x0);
@@ -105,11 +106,11 @@ __global__ __launch_bounds__(256) void transform_kernel(const TIN* __restrict__ 
     const TIN* src;
     if (CL) {
       ok = r < py && t < px * C;
-      src = in + (((size_t)b * H + y0 + r) * W + x0) * C + t;
+      src = in + ((size_t)(y0 + r) * W + x0) * C + t;
     } else {
       const int c = r / TR_P, y = r - c * TR_P;
       ok = c < C && y < py && t < px;
-      src = in + (((size_t)b * C + c) * H + y0 + y) * W + x0 + t;
+      src = in + ((size_t)c * H + y0 + y) * W + x0 + t;
     }
     v[k] = ok ? *src : (TIN)0;
   }
@@ -142,8 +143,57 @@ __global__ __launch_bounds__(256) void transform_kernel(const TIN* __restrict__ 
     const float* pc = CL ? patch + c : patch + c * TR_P * PITCH;
     const float v00 = pc[(ya - y0) * PITCH + (xa - x0) * XS], v01 = pc[(ya - y0) * PITCH + (xb - x0) * XS];
     const float v10 = pc[(yb - y0) * PITCH + (xa - x0) * XS], v11 = pc[(yb - y0) * PITCH + (xb - x0) * XS];
-    out[(((size_t)b * C + c) * O + i) * O + j] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+    out[((size_t)c * O + i) * O + j] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
   }
+}
+
+template <int C, bool CL, typename TIN = float>
+__global__ __launch_bounds__(256) void transform_kernel(const TIN* __restrict__ in, const float* __restrict__ lut, int H,
+                                                         int W, int O, float* __restrict__ out) {
+  extern __shared__ float patch[];
+  const size_t b = blockIdx.z;
+  transform_tile<C, CL, TIN>(in + b * H * W * C, lut, H, W, O, out + b * C * O * O, blockIdx.y, blockIdx.x, patch);
+}
+
+// A trainer batch straight out of a device-resident coded cache (replay.DeviceCache): block (tj, ti, b) gathers row
+// rows[b] of `codes` [n,H,W,C] and runs the coded tile above on it; the first tile of each row also gathers the row's
+// vec [5], its target future[row, 0::stride][:T] (transforms.downsample_target) and, if asked, its CIL mode with
+// STOP (1) rewritten to FORWARD (0) (cil/model.py:166-168).  Row offsets are 64-bit: 100 k observations of
+// 200 x 200 x 2 codes are 8 GB.  A row outside [0, n) reads nothing and yields NaN outputs.
+template <int C>
+__global__ __launch_bounds__(256) void gather_batch_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lut,
+                                                           const int64_t* __restrict__ rows, int64_t n, int H, int W, int O,
+                                                           const float* __restrict__ vec, const float* __restrict__ future,
+                                                           int L, int T, int stride, const float* __restrict__ mode,
+                                                           float* __restrict__ visual, float* __restrict__ vec_out,
+                                                           float* __restrict__ target, float* __restrict__ mode_out) {
+  extern __shared__ float patch[];
+  const int b = blockIdx.z;
+  const int64_t row = rows[b];
+  const bool valid = row >= 0 && row < n;
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && blockIdx.y == 0) {
+    const float nan = __builtin_nanf("");
+    if (tid < 5) vec_out[(size_t)b * 5 + tid] = valid ? vec[row * 5 + tid] : nan;
+    for (int e = tid; e < 2 * T; e += 256) {
+      const int t = e >> 1, d = e & 1;
+      target[(size_t)b * 2 * T + e] = valid ? future[(row * L + (int64_t)t * stride) * 2 + d] : nan;
+    }
+    if (mode_out != nullptr && tid == 0) {
+      const float m = valid ? mode[row] : nan;
+      mode_out[b] = m == 1.f ? 0.f : m;
+    }
+  }
+  float* out = visual + (size_t)b * C * O * O;
+  if (!valid) {  // uniform over the block
+    const int i0 = blockIdx.y * TR_T, j0 = blockIdx.x * TR_T;
+    for (int e = tid; e < C * TR_T * TR_T; e += 256) {
+      const int jl = e % TR_T, il = (e / TR_T) % TR_T, c = e / (TR_T * TR_T);
+      if (i0 + il < O && j0 + jl < O) out[((size_t)c * O + i0 + il) * O + j0 + jl] = __builtin_nanf("");
+    }
+    return;
+  }
+  transform_tile<C, true, uint8_t>(codes + row * H * W * C, lut, H, W, O, out, blockIdx.y, blockIdx.x, patch);
 }
 
 template <int C, bool CL, typename TIN = float>
@@ -1154,6 +1204,47 @@ hipError_t launch_transform_coded(const uint8_t* in, const float* lut, int B, in
   if (C == 2) launch_transform_tiled<2, true, uint8_t>(in, lut, B, H, W, out_hw, out, s);
   if (C == 3) launch_transform_tiled<3, true, uint8_t>(in, lut, B, H, W, out_hw, out, s);
   return hipGetLastError();
+}
+
+template <int C>
+static hipError_t launch_gather_batch_c(const uint8_t* codes, const float* lut, const int64_t* rows, int B, int64_t n, int H,
+                                        int W, int O, const float* vec, const float* future, int L, int T, int stride,
+                                        const float* mode, float* visual, float* vec_out, float* target, float* mode_out,
+                                        hipStream_t s) {
+  constexpr int ROW = TR_P * C;
+  const size_t lds = ((size_t)(ROW + 1) * TR_P + 256) * sizeof(float);  // C = 4: 74.3 KB patch + 1 KB table
+  if (lds > 64 * 1024) {  // per device: above 64 KB the dynamic LDS size needs the opt-in (160 KB per CU on gfx950)
+    static bool attr_set[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError();
+    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_batch_kernel<C>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      attr_set[dev] = true;
+    }
+  }
+  const int tiles = (O + TR_T - 1) / TR_T;
+  hipLaunchKernelGGL((gather_batch_kernel<C>), dim3(tiles, tiles, B), dim3(256), lds, s, codes, lut, rows, n, H, W, O, vec,
+                     future, L, T, stride, mode, visual, vec_out, target, mode_out);
+  return hipGetLastError();
+}
+
+bool gather_batch_supported(int C, int H, int W, int out_hw) {
+  const float scale = out_hw > 1 ? (float)((H > W ? H : W) - 1) / (float)(out_hw - 1) : 0.f;
+  return scale * (TR_T - 1) + 3.f <= (float)TR_P && C >= 1 && C <= 4;
+}
+hipError_t launch_gather_batch(const uint8_t* codes, const float* lut, const int64_t* rows, int B, int64_t n, int C, int H,
+                               int W, int out_hw, const float* vec, const float* future, int L, int T, int stride,
+                               const float* mode, float* visual, float* vec_out, float* target, float* mode_out,
+                               hipStream_t s) {
+  switch (C) {
+    case 1: return launch_gather_batch_c<1>(codes, lut, rows, B, n, H, W, out_hw, vec, future, L, T, stride, mode, visual, vec_out, target, mode_out, s);
+    case 2: return launch_gather_batch_c<2>(codes, lut, rows, B, n, H, W, out_hw, vec, future, L, T, stride, mode, visual, vec_out, target, mode_out, s);
+    case 3: return launch_gather_batch_c<3>(codes, lut, rows, B, n, H, W, out_hw, vec, future, L, T, stride, mode, visual, vec_out, target, mode_out, s);
+    case 4: return launch_gather_batch_c<4>(codes, lut, rows, B, n, H, W, out_hw, vec, future, L, T, stride, mode, visual, vec_out, target, mode_out, s);
+  }
+  return hipErrorInvalidValue;
 }
 
 namespace {

@@ -474,6 +474,26 @@ int rip_transform(const float* lidar_dev, int B, int C, int H, int W, int channe
   return RIP_OK;
 }
 
+int rip_gather_batch_u8(const uint8_t* codes_dev, const float* lut_dev, const int64_t* rows_dev, int B, int64_t n, int C,
+                        int H, int W, int out_hw, const float* vec_dev, const float* future_dev, int L, int T, int stride,
+                        const float* mode_dev, float* visual_dev, float* vec_out_dev, float* target_dev,
+                        float* mode_out_dev, rip_stream_t stream) {
+  REQUIRE(codes_dev != nullptr && lut_dev != nullptr && rows_dev != nullptr && vec_dev != nullptr && future_dev != nullptr &&
+              visual_dev != nullptr && vec_out_dev != nullptr && target_dev != nullptr,
+          "NULL argument");
+  REQUIRE(mode_out_dev == nullptr || mode_dev != nullptr, "mode_out_dev needs mode_dev");
+  REQUIRE(B >= 1 && n >= 1 && H >= 1 && W >= 1 && out_hw >= 1, "bad shape B=%d n=%lld H=%d W=%d out=%d", B, (long long)n,
+          H, W, out_hw);
+  REQUIRE(B <= 65535, "B=%d above the grid's z limit 65535", B);
+  REQUIRE(gather_batch_supported(C, H, W, out_hw), "coded BEV: C=%d H=%d W=%d out=%d not supported (C <= 4, down-sampling by <= 2)",
+          C, H, W, out_hw);
+  REQUIRE(L >= 1 && T >= 1 && stride >= 1 && (L + stride - 1) / stride == T,
+          "future[:, 0::%d] of L=%d steps does not give T=%d steps", stride, L, T);
+  HIP_TRY(launch_gather_batch(codes_dev, lut_dev, rows_dev, B, n, C, H, W, out_hw, vec_dev, future_dev, L, T, stride, mode_dev,
+                              visual_dev, vec_out_dev, target_dev, mode_out_dev, (hipStream_t)stream));
+  return RIP_OK;
+}
+
 // Does an fp32 encode of B observations take the one-launch kernel?  Never after its protocol failed once.
 static bool mega_applies(const rip_handle* h, int B) {
   if (h->mega_max_b <= 0 || B > h->mega_max_b || h->encoder_mega != 1) return false;

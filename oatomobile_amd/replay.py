@@ -307,7 +307,7 @@ CACHE_FILES = ("codes.npy", "lut.npy", "vec.npy", "goal.npy")
 
 
 def pack_cache(files: Sequence[str], out_dir: str, num_goals: int = 10, goal_stride: int = 8, channels: Optional[int] = None,
-               chunk: int = 256, workers: Optional[int] = None) -> "PackedCache":
+               chunk: int = 256, workers: Optional[int] = None, targets: bool = False) -> "PackedCache":
   """One-time conversion of datum files (the reference's compressed `.npz`, datasets/carla.py:107-164 — they stay the
   source of truth) into a packed cache under `out_dir`:
 
@@ -318,6 +318,12 @@ def pack_cache(files: Sequence[str], out_dir: str, num_goals: int = 10, goal_str
                                 of its own, after the positive ones), padded with NaN
     vec.npy   [n,5]    float32  velocity[3], is_at_traffic_light, traffic_light_state
     goal.npy  [n,G,2]  float32  `goal_from_future(player_future)`
+
+  `targets=True` adds the training targets (`DeviceCache`, `_PackedTrainer.train_epoch`):
+
+    future.npy [n,L,2] float32  `player_future[:, :2]` (L = 80 for the reference's `process()`)
+    mode.npy   [n]     float32  the label `load_datum(mode=True)` gives (datasets/carla.py:148-162), as the datum says:
+                                the CIL model's STOP -> FORWARD rewrite is applied when a batch is gathered
 
   `lut[codes]` reproduces `load_datum(...)["lidar"]` bit for bit — compared as uint32 patterns per chunk while packing,
   so the sign of a zero survives; more than 256 distinct values or a NaN raise ValueError: such data is not a clipped
@@ -336,6 +342,7 @@ def pack_cache(files: Sequence[str], out_dir: str, num_goals: int = 10, goal_str
   os.makedirs(out_dir, exist_ok=True)
   first = load_datum(files[0])
   H, W, C = first["lidar"].shape
+  L = int(first["player_future"].shape[0]) if targets else 0
   if channels is not None and C != channels:
     raise ValueError("pack_cache: datums have %d BEV channels, expected %d" % (C, channels))
   shape = (n, H, W, C)
@@ -346,9 +353,11 @@ def pack_cache(files: Sequence[str], out_dir: str, num_goals: int = 10, goal_str
   workers = max(1, min(int(workers), (n + chunk - 1) // chunk))
   vec = np.empty((n, 5), np.float32)
   goal = np.empty((n, num_goals, 2), np.float32)
+  future = np.empty((n, L, 2), np.float32) if targets else None
+  mode = np.empty((n,), np.float32) if targets else None
   spans = []  # (row0, rows, table the rows were coded against)
   if workers == 1:
-    spans, vec, goal = _datum.pack_span(files, 0, out_dir, shape, num_goals, goal_stride, chunk)
+    spans, vec, goal, future, mode = _datum.pack_span(files, 0, out_dir, shape, num_goals, goal_stride, chunk, L)
   else:
     import json
     import subprocess
@@ -360,6 +369,8 @@ def pack_cache(files: Sequence[str], out_dir: str, num_goals: int = 10, goal_str
       for w, i0 in enumerate(range(0, n, per)):
         job = dict(files=files[i0:i0 + per], i0=i0, out_dir=os.path.abspath(out_dir), shape=list(shape),
                    num_goals=num_goals, goal_stride=goal_stride, chunk=chunk, result=os.path.join(tmp, "r%d.npz" % w))
+        if targets:
+          job["future_len"] = L
         path = os.path.join(tmp, "j%d.json" % w)
         with open(path, "w") as fh:
           json.dump(job, fh)
@@ -379,6 +390,8 @@ def pack_cache(files: Sequence[str], out_dir: str, num_goals: int = 10, goal_str
           with np.load(job["result"]) as r:
             i0, m = job["i0"], len(job["files"])
             vec[i0:i0 + m], goal[i0:i0 + m] = r["vec"], r["goal"]
+            if targets:
+              future[i0:i0 + m], mode[i0:i0 + m] = r["future"], r["mode"]
             off = 0
             for (row0, rows), size in zip(r["rows"], r["sizes"]):
               spans.append((int(row0), int(rows), r["tables"][off:off + int(size)].copy()))
@@ -403,13 +416,17 @@ def pack_cache(files: Sequence[str], out_dir: str, num_goals: int = 10, goal_str
   np.save(os.path.join(out_dir, "lut.npy"), lut)
   np.save(os.path.join(out_dir, "vec.npy"), vec)
   np.save(os.path.join(out_dir, "goal.npy"), goal)
+  if targets:
+    np.save(os.path.join(out_dir, "future.npy"), future)
+    np.save(os.path.join(out_dir, "mode.npy"), mode)
   return PackedCache(out_dir)
 
 
 class PackedCache:
   """A cache written by `pack_cache`, memory-mapped: `len()`, `lidar(i)` (the float32 BEV `load_datum` would give),
   and `batches(batch_size)` -> host tensors `(codes [n,H,W,C] uint8, vec [n,5], goal [n,G,2])` in pinned staging
-  buffers (two slots: the tensors of a batch stay valid while the next one is being filled)."""
+  buffers (two slots: the tensors of a batch stay valid while the next one is being filled).  A cache packed with
+  `targets=True` also has `future` [n,L,2] and `mode` [n] (`has_targets`; both None otherwise)."""
 
   def __init__(self, cache_dir: str) -> None:
     self.dir = cache_dir
@@ -420,6 +437,17 @@ class PackedCache:
     if not (self.codes.dtype == np.uint8 and self.codes.ndim == 4 and self.lut.shape == (256,) and
             self.vec.shape == (self.codes.shape[0], 5) and self.goal.shape[0] == self.codes.shape[0]):
       raise ValueError("%s is not a packed replay cache" % cache_dir)
+    self.future = self.mode = None
+    if os.path.exists(os.path.join(cache_dir, "future.npy")):
+      self.future = np.load(os.path.join(cache_dir, "future.npy"), mmap_mode="r")
+      self.mode = np.load(os.path.join(cache_dir, "mode.npy"), mmap_mode="r")
+      if not (self.future.ndim == 3 and self.future.shape[0] == len(self) and self.future.shape[2] == 2 and
+              self.mode.shape == (len(self),)):
+        raise ValueError("%s: future.npy / mode.npy do not match the cache" % cache_dir)
+
+  @property
+  def has_targets(self) -> bool:
+    return self.future is not None
 
   def __len__(self) -> int:
     return int(self.codes.shape[0])
@@ -454,6 +482,123 @@ class PackedCache:
         np.copyto(v.numpy()[:m], self.vec[i0:i0 + m])
         np.copyto(g.numpy()[:m], self.goal[i0:i0 + m])
         yield c[:m], v[:m], g[:m]
+
+
+def downsample_stride(L: int, T: int) -> int:
+  """transforms.downsample_target (torch/transforms.py:23-31) keeps `future[:, 0::L // T]`: that stride, or ValueError
+  when the slice does not have exactly T steps (the reference would hand the model a target of another length)."""
+  L, T = int(L), int(T)
+  stride = L // T if T >= 1 else 0
+  if stride < 1 or len(range(0, L, stride)) != T:
+    raise ValueError("a future of %d steps downsampled by 0::%d has %d steps, not num_timesteps_to_keep=%d" %
+                     (L, max(stride, 0), len(range(0, L, stride)) if stride >= 1 else 0, T))
+  return stride
+
+
+class DeviceCache:
+  """A `pack_cache(..., targets=True)` cache resident in device memory, for training by the epoch
+  (`DIMTrainer.train_epoch` / `CILTrainer.train_epoch`):
+
+      data = DeviceCache(PackedCache(cache_dir), device)    # one upload: codes, lut, vec, future, mode
+      batch = data.batch(rows, T, mode=False)                # the dict the trainers take, one kernel launch
+
+  `batch(rows, T)` gathers rows `rows` (an int64 device tensor, or host indices that are range-checked) with
+  `rip_gather_batch_u8`: `visual_features` [B,C,100,100] bit-identical to `transform_visual(lut[codes[rows]],
+  channels_last=True)`, `velocity` [B,3], `is_at_traffic_light` [B,1], `traffic_light_state` [B,1] (views of one [B,5]
+  tensor), `player_future` [B,T,2] = `future[rows, 0::L // T]` (the model's `transform`), and with `mode=True` the CIL
+  `mode` [B,1] with STOP -> FORWARD (cil/model.py:166-168).  A device row outside [0, n) yields NaN for its row.
+
+  The whole cache must fit in device memory (80 KB per 200 x 200 x 2 observation: 100 k observations are 8 GB); the
+  constructor checks `torch.cuda.mem_get_info` first and raises MemoryError with the sizes otherwise.  Caches larger
+  than device memory (a streamed variant) are not supported."""
+
+  OUT_HW = 100
+
+  def __init__(self, cache, device=None, staging_bytes: int = 64 << 20) -> None:
+    if isinstance(cache, str):
+      cache = PackedCache(cache)
+    if not cache.has_targets:
+      raise ValueError("DeviceCache: %s has no training targets; pack it with pack_cache(..., targets=True)" % cache.dir)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+      raise RuntimeError("DeviceCache needs a ROCm device, got %s (no CPU path)" % dev)
+    if dev.index is None:
+      dev = torch.device("cuda", torch.cuda.current_device())
+    self.device = dev
+    n, H, W, C = (int(v) for v in cache.codes.shape)
+    L = int(cache.future.shape[1])
+    self.n, self.H, self.W, self.C, self.L = n, H, W, C, L
+    need = n * H * W * C + n * 4 * (5 + 2 * L + 1) + 256 * 4
+    free, total = torch.cuda.mem_get_info(dev)
+    if need > free:
+      raise MemoryError("DeviceCache: the cache needs %.2f GB of device memory (%d observations: codes %.2f GB, targets "
+                        "%.1f MB); %s has %.2f GB free of %.2f GB.  Caches larger than device memory are not supported." %
+                        (need / 1e9, n, n * H * W * C / 1e9, n * 4 * (5 + 2 * L + 1) / 1e6, dev, free / 1e9, total / 1e9))
+    with torch.cuda.device(dev):
+      self.codes = torch.empty((n, H, W, C), dtype=torch.uint8, device=dev)
+      per = max(1, int(staging_bytes) // (H * W * C))
+      stream = torch.cuda.current_stream(dev)
+      slots = [torch.empty((min(per, n), H, W, C), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+      done = [None, None]
+      for k, i0 in enumerate(range(0, n, per)):  # memmap -> pinned slot -> device, the other slot's copy in flight
+        m = min(per, n - i0)
+        j = k & 1
+        if done[j] is not None:
+          done[j].synchronize()
+        np.copyto(slots[j].numpy()[:m], cache.codes[i0:i0 + m])
+        self.codes[i0:i0 + m].copy_(slots[j][:m], non_blocking=True)
+        done[j] = torch.cuda.Event()
+        done[j].record(stream)
+      self.lut = torch.from_numpy(np.ascontiguousarray(cache.lut, np.float32)).to(dev)
+      self.vec = torch.from_numpy(np.ascontiguousarray(cache.vec, np.float32)).to(dev)
+      self.future = torch.from_numpy(np.array(cache.future, np.float32)).to(dev)
+      self.mode = torch.from_numpy(np.array(cache.mode, np.float32)).to(dev)
+      torch.cuda.synchronize(dev)  # the pinned slots are freed on return
+
+  def __len__(self) -> int:
+    return self.n
+
+  @property
+  def channels(self) -> int:
+    return self.C
+
+  def rows(self, rows) -> torch.Tensor:
+    """`rows` as a contiguous int64 device tensor; host indices are range-checked here (device ones are not: that
+    would synchronise — the kernel turns an out-of-range row into NaN outputs instead)."""
+    if isinstance(rows, torch.Tensor) and rows.is_cuda:
+      if rows.dtype.is_floating_point or rows.dim() != 1:
+        raise ValueError("rows must be a 1-D integer tensor, got %s %s" % (rows.dtype, tuple(rows.shape)))
+      return rows.to(self.device, torch.int64).contiguous()
+    r = np.asarray(rows.cpu() if isinstance(rows, torch.Tensor) else rows)
+    if r.ndim != 1 or not np.issubdtype(r.dtype, np.integer):
+      raise ValueError("rows must be 1-D integers, got %s %s" % (r.dtype, r.shape))
+    if r.size and (r.min() < 0 or r.max() >= self.n):
+      raise IndexError("rows outside [0, %d): min %d, max %d" % (self.n, r.min(), r.max()))
+    return torch.from_numpy(r.astype(np.int64)).to(self.device)
+
+  def batch(self, rows, T: int, mode: bool = False):
+    """The trainer batch of `rows` with a target of `T` steps (ValueError if `future[:, 0::L // T]` has not T steps)."""
+    from oatomobile_amd import _lib
+    stride = downsample_stride(self.L, T)
+    rows = self.rows(rows)
+    B = int(rows.numel())
+    if B == 0:
+      raise ValueError("DeviceCache.batch: no rows")
+    dev = self.device
+    visual = torch.empty((B, self.C, self.OUT_HW, self.OUT_HW), device=dev)
+    vec = torch.empty((B, 5), device=dev)
+    target = torch.empty((B, T, 2), device=dev)
+    mode_out = torch.empty((B, 1), device=dev) if mode else None
+    with torch.cuda.device(dev):  # stateless entry point: launches on the current device
+      _lib.check(_lib.load().rip_gather_batch_u8(
+          _lib.ptr(self.codes, torch.uint8), _lib.ptr(self.lut), _lib.ptr(rows, torch.int64), B, self.n, self.C, self.H,
+          self.W, self.OUT_HW, _lib.ptr(self.vec), _lib.ptr(self.future), self.L, int(T), stride, _lib.ptr(self.mode),
+          _lib.ptr(visual), _lib.ptr(vec), _lib.ptr(target), _lib.ptr(mode_out), _lib.current_stream(dev)))
+    out = dict(visual_features=visual, velocity=vec[:, 0:3], is_at_traffic_light=vec[:, 3:4],
+               traffic_light_state=vec[:, 4:5], player_future=target)
+    if mode:
+      out["mode"] = mode_out
+    return out
 
 
 def replay_cache(agent, cache: "PackedCache", batch_size: int, interpolate: bool = False, begin: int = 0,

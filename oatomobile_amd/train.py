@@ -5,6 +5,7 @@ the `rip_train_*` entry points of librip_hip.so (csrc/train.hip, csrc/flow.hip),
     trainer = DIMTrainer(model, lr=1e-3)                 # optim.Adam(model.parameters(), lr) (train.py:112-116)
     loss = trainer.train_step(batch)                     # train_step(model, optimizer, batch) (train.py:175-213)
     trainer.sync_to_model()                              # updated weights (and BN buffers) back into `model`
+    loss = trainer.train_epoch(data, 512, generator=g)   # train_epoch (train.py:215-227) from a replay.DeviceCache
 
 `batch` is what the reference's `transform` closure produces (train.py:122-134): `visual_features [B,C,100,100]`,
 `velocity [B,3]`, `is_at_traffic_light [B,1]`, `traffic_light_state [B,1]`, `player_future [B,4,>=2]`, on the device.
@@ -161,6 +162,111 @@ class _PackedTrainer:
                                         _lib.current_stream(self._device)))
     return buf.permute(0, 3, 1, 2)
 
+  # ---- by the epoch, from a device-resident cache (replay.DeviceCache) ----
+  _epoch_mode = False  # does the batch carry the CIL `mode`
+
+  def _epoch_horizon(self) -> int:
+    raise NotImplementedError
+
+  def _target_noise(self, target: torch.Tensor, rows: int, a: int, b: int, generator) -> Optional[torch.Tensor]:
+    """The perturbed target `y` of this rank's slice [a, b) of a global batch of `rows` rows, or None (no noise)."""
+    return None
+
+  def _rank_world(self):
+    if self._group is None:
+      return 0, 1
+    return torch.distributed.get_rank(self._group), torch.distributed.get_world_size(self._group)
+
+  def train_epoch(self, data, batch_size: int, *, generator: Optional[torch.Generator] = None, clip: bool = False) -> float:
+    """One epoch of the reference's `train_epoch` (dim/train.py:215-228, cil/train.py:192-206) over `data`, a
+    `replay.DeviceCache`: `DataLoader(shuffle=True, drop_last=False)` semantics, `train_step` per batch, and the
+    mean of the per-batch losses (`loss / len(dataloader)`) as a float.
+
+    The random draws come from `generator` (a generator on this trainer's device; None = torch's default one) in
+    this order: `torch.randperm(len(data))` once (kept in `self.last_permutation`), then per batch the target noise
+    N(0, noise_level^2) of shape [rows, T, 2] (DIM only) and the dropout keep mask (`bernoulli_(0.8)` of shape
+    [rows, 1280], scaled by 1 / 0.8).  Per-batch losses stay on the device (`self.last_epoch_losses`); the epoch
+    synchronises once, for its result.
+
+    With `group=` (data parallel) every rank must pass an identically seeded generator: all ranks draw the same
+    permutation, a global batch is `batch_size * world` rows and rank r trains on its `distributed.shard_range` slice
+    of it.  The noise and the mask are drawn for the whole global batch and sliced, so the generators stay in step.
+    The gradient is row-weighted: when the slices of a global batch are uneven (its last one), a rank scales its
+    batch-mean gradient by `rows_r * world / rows` before the all-reduce averages it, so the reduced gradient is the
+    mean over the global batch's rows, as one process would compute it (a rank with an empty slice contributes
+    zero).  BatchNorm statistics are per rank, as under DistributedDataParallel without SyncBatchNorm.  The per-batch
+    losses are row-weighted over the ranks too (one all-reduce at the end of the epoch), so every rank returns the
+    same epoch loss."""
+    from oatomobile_amd.distributed import shard_range
+    if batch_size < 1 or batch_size > self._max_batch:
+      raise ValueError("batch_size=%d outside [1, max_batch=%d]" % (batch_size, self._max_batch))
+    if data.channels != self._C:
+      raise ValueError("the cache has %d BEV channels, the model %d" % (data.channels, self._C))
+    T = self._epoch_horizon()
+    rank, world = self._rank_world()
+    n = len(data)
+    perm = torch.randperm(n, device=self._device, generator=generator)
+    self.last_permutation = perm
+    losses, global_rows = [], []
+    gb = batch_size * world
+    for g0 in range(0, n, gb):
+      rows = min(gb, n - g0)
+      a, b = shard_range(rows, rank, world)
+      global_rows.append(rows)
+      if b == a:
+        self.grads.zero_()
+        self.apply(clip=clip)
+        losses.append(torch.zeros((), device=self._device))
+        continue
+      batch = data.batch(perm[g0 + a:g0 + b], T, mode=self._epoch_mode)
+      y = self._target_noise(batch["player_future"], rows, a, b, generator)
+      keep = torch.empty(rows, arch.LAST_CHANNELS, device=self._device).bernoulli_(1.0 - DROPOUT_P, generator=generator)
+      keep = keep.mul_(1.0 / (1.0 - DROPOUT_P))[a:b]
+      kw = {} if y is None else {"y": y}
+      loss = self.backward(batch, dropout_mask=keep, **kw)
+      if world > 1 and (b - a) * world != rows:  # uneven slices: row-weight this rank's share of the average
+        self.grads.mul_((b - a) * world / rows)
+      losses.append(loss * (b - a) if world > 1 else loss)
+      self.apply(clip=clip)
+    if not losses:
+      self.last_epoch_losses = torch.zeros(0, device=self._device)
+      return float("nan")
+    per_batch = torch.stack(losses)
+    if world > 1:  # sum over the ranks of rows_r * loss_r, divided by the global batch's rows
+      torch.distributed.all_reduce(per_batch, op=torch.distributed.ReduceOp.SUM, group=self._group)
+      per_batch = per_batch / torch.tensor(global_rows, dtype=per_batch.dtype, device=self._device)
+    self.last_epoch_losses = per_batch
+    return float(per_batch.mean())
+
+  def evaluate_epoch(self, data, batch_size: int, *, generator: Optional[torch.Generator] = None,
+                     shuffle: bool = False) -> float:
+    """The reference's `evaluate_epoch` (dim/train.py:253-267, cil/train.py:221-235): `evaluate_step` per batch of
+    `batch_size` rows (in order, or with `shuffle` in the order of `torch.randperm(len(data), generator=generator)`,
+    kept in `self.last_permutation`) and the mean of the per-batch means, as a float.  Evaluation uses the running
+    statistics, so every row's loss is independent of the rest of its batch: a batch larger than `max_batch` (the
+    reference validates with 5x the training batch) runs in chunks of `max_batch` rows recombined as the row-weighted
+    mean of the chunk means.  Every rank evaluates all of `data`."""
+    if batch_size < 1:
+      raise ValueError("batch_size=%d < 1" % batch_size)
+    T = self._epoch_horizon()
+    n = len(data)
+    if shuffle:
+      order = torch.randperm(n, device=self._device, generator=generator)
+      self.last_permutation = order
+    else:
+      order = torch.arange(n, device=self._device)
+    means = []
+    for g0 in range(0, n, batch_size):
+      rows = min(batch_size, n - g0)
+      total = None
+      for c0 in range(0, rows, self._max_batch):
+        m = min(self._max_batch, rows - c0)
+        loss = self.evaluate_step(data.batch(order[g0 + c0:g0 + c0 + m], T, mode=self._epoch_mode)) * m
+        total = loss if total is None else total + loss
+      means.append(total / rows)
+    self.last_epoch_losses = torch.stack(means) if means else torch.zeros(0, device=self._device)
+    return float(self.last_epoch_losses.mean()) if means else float("nan")
+
   # ---- views of the packed vectors in the reference's state_dict terms ----
   def _unpack(self, vector: torch.Tensor):
     out, pos = {}, 0
@@ -249,6 +355,15 @@ class DIMTrainer(_PackedTrainer):
       self.num_batches_tracked += 1
     return self._loss.clone()
 
+  def _epoch_horizon(self) -> int:
+    return arch.T
+
+  def _target_noise(self, target, rows, a, b, generator):
+    """train.py:184-189 for the epoch loop: N(0, noise_level^2) drawn for the whole global batch, this rank's slice
+    added to its target."""
+    noise = torch.empty((rows,) + tuple(target.shape[1:]), device=self._device).normal_(0.0, self._noise, generator=generator)
+    return target + noise[a:b]
+
   def train_step(self, batch: Mapping[str, torch.Tensor], *, y: Optional[torch.Tensor] = None,
                  dropout_mask: Optional[torch.Tensor] = None, clip: bool = False) -> torch.Tensor:
     """train.py:175-213."""
@@ -288,6 +403,11 @@ class CILTrainer(_PackedTrainer):
     self._T = int(model._output_shape[0])
     super().__init__(model, lr, weight_decay, max_batch, device, betas, eps, group)
     self.predictions = None
+
+  _epoch_mode = True
+
+  def _epoch_horizon(self) -> int:
+    return self._T
 
   def _create(self) -> int:
     _lib.check(self._lib.rip_cil_train_create(ctypes.byref(self._h), self._C, self._T, self._max_batch,

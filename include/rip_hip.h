@@ -27,8 +27,8 @@
  *   - a handle is bound to one device: every entry point that takes a handle
  *     makes that device current for the duration of the call and restores the
  *     caller's current device before returning.  The stateless entry points
- *     (rip_transform, rip_goal_likelihood, rip_lidar_bev, rip_cil_decode,
- *     rip_gather_batch_u8) launch
+ *     (rip_transform, rip_goal_likelihood, rip_goal_likelihood_vjp,
+ *     rip_lidar_bev, rip_cil_decode, rip_gather_batch_u8) launch
  *     on the caller's current device, which must own the pointers.
  *   - a handle's scratch is shared by its calls, so a handle is single-stream
  *     and not thread-safe: when consecutive calls on one handle name different
@@ -154,6 +154,30 @@ int rip_flow_inverse(rip_handle* h, int k, const float* y_dev, const float* z_de
  * goal_rows == N or 1; rows_dev [N]. */
 int rip_goal_likelihood(const float* y_dev, const float* goal_dev, int N, int goal_rows, int G, float epsilon,
                         float* rows_dev, rip_stream_t stream);
+
+/* Vector-Jacobian products of R6 / R7 (the backward of ImitativeModel._forward / _inverse under autograd): model k's
+ * flow is recomputed with a full tape and differentiated through all T steps, h_0 = z and the GRU input y_{t-1}
+ * included.  mode RIP_FLOW_VJP_FORWARD: in_dev = x [N,4,2]; cotangents g_out_dev = dL/dy [N,4,2] and
+ * g_logabsdet_dev [N]; g_log_prob_dev must be NULL; d_in_dev = dL/dx [N,4,2].  mode RIP_FLOW_VJP_INVERSE: in_dev = y;
+ * cotangents g_out_dev = dL/dx, g_log_prob_dev [N], g_logabsdet_dev [N]; d_in_dev = dL/dy.  Any cotangent may be
+ * NULL (zero); d_in_dev and dz_dev [z_rows,64] may be NULL (not wanted; both NULL launches nothing).  z_rows == N or
+ * 1; with z_rows == 1 dz is the sum over the N rows, formed without atomics in a fixed order (the same bits on every
+ * run) through workspace_dev, which must hold rip_flow_vjp_workspace_bytes(N, z_rows) bytes whenever that is > 0 and
+ * dz_dev != NULL (else it may be NULL).  The caller keeps the workspace untouched until the call's work completes on
+ * `stream`. */
+#define RIP_FLOW_VJP_FORWARD 0
+#define RIP_FLOW_VJP_INVERSE 1
+int rip_flow_vjp(rip_handle* h, int k, int mode, const float* in_dev, const float* z_dev, int N, int z_rows,
+                 const float* g_out_dev, const float* g_log_prob_dev, const float* g_logabsdet_dev, float* d_in_dev,
+                 float* dz_dev, void* workspace_dev, rip_stream_t stream);
+
+/* Bytes of rip_flow_vjp's workspace: 1 KiB x 4 x min(max(ceil(N / 4), 1), 2048) when z_rows == 1 and N > 1, else 0. */
+size_t rip_flow_vjp_workspace_bytes(int N, int z_rows);
+
+/* VJP of R9 per row: dy_dev [N,4,2] = g_rows_dev[i] x d rows[i] / dy_i, which is nonzero only at the last waypoint
+ * (y_dev, goal_dev, goal_rows, G, epsilon as rip_goal_likelihood).  The goal receives no gradient. */
+int rip_goal_likelihood_vjp(const float* y_dev, const float* goal_dev, int N, int goal_rows, int G, float epsilon,
+                            const float* g_rows_dev, float* dy_dev, rip_stream_t stream);
 
 /* Scoring mode of R5 (rip/agent.py:109-119, per plan instead of batch mean):
  * S[k,b,n] = log_prob_k - logabsdet_k (+ goal log-likelihood if goal_dev != NULL)

@@ -32,6 +32,12 @@ SIGNATURES = [
     ("rip_flow_inverse", c_int,
      [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("rip_goal_likelihood", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    ("rip_flow_vjp", c_int, [
+        c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+        c_void_p, c_void_p
+    ]),
+    ("rip_flow_vjp_workspace_bytes", c_size_t, [c_int, c_int]),
+    ("rip_goal_likelihood_vjp", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     ("rip_score", c_int,
      [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("rip_aggregate_scores", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -96,6 +96,14 @@ hipError_t launch_flow_inverse(const float* flow_w_k, const float* y, const floa
                                float* logp, float* lad, hipStream_t s);
 hipError_t launch_goal_rows(const float* y, const float* goal, int N, int goal_rows, int G, float eps, float* rows,
                             hipStream_t s);
+// VJPs of the two above (mode 0 = forward, 1 = inverse) and of launch_goal_rows (flow.hip: flow_vjp_kernel); `workspace`
+// holds flow_vjp_workspace_bytes(N, z_rows) bytes when dz is wanted (broadcast z: per-wave partial sums)
+size_t flow_vjp_workspace_bytes(int N, int z_rows);
+hipError_t launch_flow_vjp(const float* flow_w_k, int mode, const float* in, const float* z, int N, int z_rows,
+                           const float* ga, const float* glp, const float* glad, float* d_in, float* dz, void* workspace,
+                           hipStream_t s);
+hipError_t launch_goal_rows_vjp(const float* y, const float* goal, int N, int goal_rows, int G, float eps,
+                                const float* grow, float* dy, hipStream_t s);
 hipError_t launch_score(const float* flow_w, int k0, int K, const float* z, const float* y, const float* goal, int B,
                         int N, int G, float eps, float* S, hipStream_t s);
 hipError_t launch_search(const SearchArgs& a, hipStream_t s);

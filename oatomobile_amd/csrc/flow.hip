@@ -232,7 +232,11 @@ __device__ __forceinline__ void head_finish(const FlowRegs& W, float a1, float& 
   o3 = (rl(p1, 32) + rl(p1, 48)) + W.b2[3];
 }
 
-__device__ __forceinline__ Prefix chain_prefix(const FlowRegs& W, const float* w1row, float h0) {
+// SAVE: also tapes step 0 into slot 0 of `tape` (chain_forward's layout; its lane rows are not written by chain_forward)
+// plus the softplus gradients of the step-0 scale, for adjoints that run through h_0 = z (flow_vjp_kernel).
+template <bool SAVE = false>
+__device__ __forceinline__ Prefix chain_prefix(const FlowRegs& W, const float* w1row, float h0, float* tape = nullptr,
+                                               int lane = 0) {
   Prefix p;
   float gh[3], a1 = 0.f;
   matvec<true, false>(W, w1row, h0, gh, a1);
@@ -244,6 +248,19 @@ __device__ __forceinline__ Prefix chain_prefix(const FlowRegs& W, const float* w
   matvec<true, true>(W, w1row, p.h1, p.gh, a1);
   float o0, o1, o2, o3;
   head_finish(W, a1, o0, o1, o2, o3);
+  if (SAVE) {
+    float* tl = tape + lane;
+    tl[0 * 64] = h0;
+    tl[1 * 64] = r;
+    tl[2 * 64] = zg;
+    tl[3 * 64] = n;
+    tl[4 * 64] = gh[2];
+    tl[5 * 64] = a1;
+    if (lane == 0) {
+      tape[TAPE_LANE + 4] = softplus_gradf_(o2);
+      tape[TAPE_LANE + 5] = softplus_gradf_(o3);
+    }
+  }
   p.dloc0 = o0;
   p.dloc1 = o1;
   p.s0 = softplusf_(o2) + 1e-3f;
@@ -363,6 +380,32 @@ __device__ __forceinline__ ChainOut chain_forward(int mode, const FlowRegs& W, c
     yp1 = y1;
   }
   return o;
+}
+
+// Head and GRUCell adjoints of one step as used by flow_vjp_kernel.  chain_backward and flow_train_kernel spell the same
+// arithmetic inline: routing them through these helpers changes their instruction schedule, and the search and DIM
+// training kernels are kept at their committed code objects.
+// Head adjoint: da1 (lanes < 32: unit j; lanes >= 32 hold the same values) from d(dloc0, dloc1) and the gradients dos0,
+// dos1 of the pre-softplus scale outputs; `a1` is the pre-ReLU head activation of the step.
+__device__ __forceinline__ float head_adjoint(const FlowRegs& W, float a1, float dd0, float dd1, float dos0, float dos1,
+                                              bool upper) {
+  const float part = W.w2a * (upper ? dos0 : dd0) + W.w2b * (upper ? dos1 : dd1);
+  const float da1 = xor32_sum(part);
+  return a1 > 0.f ? da1 : 0.f;
+}
+
+// GRUCell adjoint of one step (gate order r, z, n), dh = dL/dh_{t+1}, tape (hprev, r, zg, n, ghn) of that step.
+// Out: the pre-activation gradients dpr, dpz, dpn (= d gi_n), dghn = d gh_n, and the direct path dhdir = dL/dh_t via z*h.
+__device__ __forceinline__ void gru_adjoint(float dh, float hprev, float r, float zg, float n, float ghn, float& dhdir,
+                                            float& dpr, float& dpz, float& dpn, float& dghn) {
+  const float dn = dh * (1.0f - zg);
+  const float dzg = dh * (hprev - n);
+  dhdir = dh * zg;
+  dpn = dn * (1.0f - n * n);
+  const float dr = dpn * ghn;
+  dghn = dpn * r;
+  dpr = dr * r * (1.0f - r);
+  dpz = dzg * zg * (1.0f - zg);
 }
 
 // Adjoint of one chain pass.
@@ -1393,6 +1436,150 @@ __global__ __launch_bounds__(256) void flow_train_kernel(const float* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Vector-Jacobian products of AutoregressiveFlow._forward / _inverse (the autograd backward of model.py's methods).
+// One wave per row, grid-stride over rows, weights as in flow_rows_kernel.  Each row recomputes its forward with
+// chain_prefix<true> / chain_forward<true> (the operations of flow_rows_kernel, so the gradient is taken at the primal
+// values the caller received) and a full tape, step 0 included (h_0 = z is an input here), then runs the adjoint
+// through all T steps, the GRU-input path y_{t-1} -> step t included:
+//   MODE_FWD  in = x, cotangents ga = dL/dy [N,8], glad = dL/dlogabsdet [N]            -> d_in = dL/dx
+//   MODE_INV  in = y, cotangents ga = dL/dx [N,8], glp = dL/dlog_prob, glad            -> d_in = dL/dy
+// (log_prob = -|x|^2/2 - 4 log 2pi folds into dL/dx as ga - glp x).  NULL cotangents are zero; d_in / dz NULL = not
+// wanted.  dz: per row into dz[row], or (dz_part != NULL: broadcast z over N > 1 rows) each wave sums its rows' dz in
+// row order and stores the sum to dz_part[blockIdx.x * nw + wave] (every wave writes its slot), reduced by
+// dz_reduce_kernel: no float atomics, the same bits on every run.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void flow_vjp_kernel(int mode, const float* __restrict__ blob,
+                                                        const float* __restrict__ in, const float* __restrict__ z,
+                                                        int N, int z_rows, const float* __restrict__ ga,
+                                                        const float* __restrict__ glp, const float* __restrict__ glad,
+                                                        float* __restrict__ d_in, float* __restrict__ dz,
+                                                        float* __restrict__ dz_part) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* w1 = smem;                                          // W1_LDS
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  float* tape = smem + W1_LDS + wave * (TAPE + 24);          // per wave: tape, then 8 in, 8 cotangents, 8 out
+  float* my_in = tape + TAPE;
+  float* my_g = my_in + 8;
+  float* my_out = my_g + 8;
+  stage_w1(w1, blob, tid, blockDim.x);
+  FlowRegs W;
+  load_flow_regs(W, blob, lane);
+  __syncthreads();
+  const float* w1row = w1 + (lane & 31) * W1_STRIDE;
+  const bool upper = lane >= 32;
+  const bool want_dz = dz != nullptr || dz_part != nullptr;
+  // MODE_INV: dL/du_t through the GRU input reaches only dy; MODE_FWD: it is part of dL/dy_{t-1}, which reaches dx and dz
+  const bool need_du = mode == MODE_FWD || d_in != nullptr;
+  const bool bcast = z_rows == 1;
+  float dz_sum = 0.f;
+  Prefix pre;
+  bool first = true;
+  for (int row = blockIdx.x * nw + wave; row < N; row += gridDim.x * nw) {
+    if (lane < 8) {
+      my_in[lane] = in[(size_t)row * 8 + lane];
+      my_g[lane] = ga != nullptr ? ga[(size_t)row * 8 + lane] : 0.f;
+    }
+    // z_rows == 1: the prefix and its tape (slot 0's lane rows, which chain_forward leaves alone) are computed once
+    if (first || !bcast) pre = chain_prefix<true>(W, w1row, z[(size_t)(bcast ? 0 : row) * 64 + lane], tape, lane);
+    first = false;
+    __builtin_amdgcn_wave_barrier();
+    chain_forward<true>(mode, W, w1row, pre, my_in, mode == MODE_FWD ? my_out : nullptr, tape, lane);
+    __builtin_amdgcn_wave_barrier();
+    const float gl = glad != nullptr ? glad[row] : 0.f;
+    const float gp = (mode == MODE_INV && glp != nullptr) ? glp[row] : 0.f;
+    float dhdir = 0.f, dpr = 0.f, dpz = 0.f, dghn = 0.f;
+    float carry0 = 0.f, carry1 = 0.f;
+#pragma unroll 1
+    for (int t = T - 1; t >= 0; --t) {
+      const float* tu = tape + TAPE_LANE + t * 8;
+      const float x0 = tu[0], x1 = tu[1], s0 = tu[2], s1 = tu[3], sg0 = tu[4], sg1 = tu[5];
+      float dd0, dd1, dos0, dos1;  // d(dloc), d(pre-softplus scale) of step t
+      if (mode == MODE_FWD) {  // y_t = y_{t-1} + dloc_t + s_t x_t
+        const float D0 = my_g[2 * t] + carry0, D1 = my_g[2 * t + 1] + carry1;  // dL/dy_t, all paths
+        if (lane == 0) {
+          my_out[2 * t] = D0 * s0;
+          my_out[2 * t + 1] = D1 * s1;
+        }
+        dd0 = D0;
+        dd1 = D1;
+        dos0 = (D0 * x0 + gl * rcpf_(s0)) * sg0;
+        dos1 = (D1 * x1 + gl * rcpf_(s1)) * sg1;
+      } else {  // x_t = (y_t - y_{t-1} - dloc_t) / s_t
+        const float i0 = rcpf_(s0), i1 = rcpf_(s1);
+        const float G0 = fmaf(-gp, x0, my_g[2 * t]), G1 = fmaf(-gp, x1, my_g[2 * t + 1]);  // dL/dx_t
+        const float gs0 = G0 * i0, gs1 = G1 * i1;
+        if (lane == 0) {
+          my_out[2 * t] = gs0 + carry0;  // own dx_t/dy_t plus what step t+1 sent back
+          my_out[2 * t + 1] = gs1 + carry1;
+        }
+        dd0 = -gs0;
+        dd1 = -gs1;
+        dos0 = (gl - G0 * x0) * i0 * sg0;  // dL/ds = (glad - G x) / s
+        dos1 = (gl - G1 * x1) * i1 * sg1;
+      }
+      if (t == 0 && !want_dz) break;  // step 0's hidden path only reaches z
+      const float* tl = tape + t * TAPE_Q * 64 + lane;
+      const float da1 = head_adjoint(W, tl[5 * 64], dd0, dd1, dos0, dos1, upper);
+      const float da1h = upper ? 0.f : da1;  // rows of W1 are duplicated in both halves
+      const float dh = transposed_matvec(W, w1row, da1h, dpr, dpz, dghn, lane) + dhdir;  // dL/dh_{t+1}
+      float dpn;
+      gru_adjoint(dh, tl[0 * 64], tl[1 * 64], tl[2 * 64], tl[3 * 64], tl[4 * 64], dhdir, dpr, dpz, dpn, dghn);
+      if (t > 0) {  // dL/dy_{t-1} through step t's location term and its GRU input
+        float du0 = 0.f, du1 = 0.f;
+        if (need_du) {
+          du0 = wave_sum(fmaf(W.wih[0][0], dpr, fmaf(W.wih[1][0], dpz, W.wih[2][0] * dpn)));
+          du1 = wave_sum(fmaf(W.wih[0][1], dpr, fmaf(W.wih[1][1], dpz, W.wih[2][1] * dpn)));
+        }
+        carry0 = dd0 + du0;
+        carry1 = dd1 + du1;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (d_in != nullptr && lane < 8) d_in[(size_t)row * 8 + lane] = my_out[lane];
+    if (want_dz) {
+      const float dzr = transposed_matvec(W, w1row, 0.f, dpr, dpz, dghn, lane) + dhdir;  // dL/dh_0
+      if (dz_part != nullptr) {
+        dz_sum += dzr;
+      } else {
+        dz[(size_t)row * 64 + lane] = dzr;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (dz_part != nullptr) dz_part[((size_t)blockIdx.x * nw + wave) * 64 + lane] = dz_sum;
+}
+
+// dz[j] = sum over the P wave partials of flow_vjp_kernel, in a fixed order (16 strided partial sums, then their sum)
+__global__ __launch_bounds__(1024) void dz_reduce_kernel(const float* __restrict__ part, int P, float* __restrict__ dz) {
+  __shared__ float acc[16][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float s = 0.f;
+  for (int p = w; p < P; p += 16) s += part[(size_t)p * 64 + lane];
+  acc[w][lane] = s;
+  __syncthreads();
+  if (w == 0) {
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t += acc[i][lane];
+    dz[lane] = t;
+  }
+}
+
+// dy[i] = grow[i] * d goal_ll / dy at the last waypoint, zero elsewhere (no gradient into the goal)
+__global__ void goal_rows_vjp_kernel(const float* __restrict__ y, const float* __restrict__ goal, int N, int goal_rows,
+                                     int G, float eps, const float* __restrict__ grow, float* __restrict__ dy) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const float* g = goal + (size_t)(goal_rows == 1 ? 0 : i) * G * 2;
+  float g0, g1;
+  (void)goal_ll(g, G, eps, y[(size_t)i * 8 + 6], y[(size_t)i * 8 + 7], &g0, &g1);
+  const float c = grow[i];
+  float4* o = reinterpret_cast<float4*>(dy + (size_t)i * 8);
+  o[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+  o[1] = make_float4(0.f, 0.f, c * g0, c * g1);
+}
+
 // reference tensor layout -> the lane-major FW_* blob of flow.h (what fold_and_pack does on the host for inference)
 __global__ void flow_relayout_kernel(const float* __restrict__ wih, const float* __restrict__ whh,
                                      const float* __restrict__ bih, const float* __restrict__ bhh,
@@ -1484,6 +1671,30 @@ hipError_t launch_flow_inverse(const float* blob, const float* y, const float* z
   const size_t lds = (W1_LDS + 4 * 16) * sizeof(float);
   hipLaunchKernelGGL(flow_rows_kernel, dim3(rows_grid(N)), dim3(256), lds, s, MODE_INV, blob, y, z, N, z_rows, x,
                      logp, lad);
+  return hipGetLastError();
+}
+
+size_t flow_vjp_workspace_bytes(int N, int z_rows) {
+  return (z_rows == 1 && N > 1) ? (size_t)rows_grid(N) * 4 * 64 * sizeof(float) : 0;
+}
+
+hipError_t launch_flow_vjp(const float* blob, int mode, const float* in, const float* z, int N, int z_rows,
+                           const float* ga, const float* glp, const float* glad, float* d_in, float* dz, void* workspace,
+                           hipStream_t s) {
+  const size_t lds = (W1_LDS + 4 * (TAPE + 24)) * sizeof(float);
+  const int grid = rows_grid(N);
+  float* part = (dz != nullptr && flow_vjp_workspace_bytes(N, z_rows) > 0) ? static_cast<float*>(workspace) : nullptr;
+  hipLaunchKernelGGL(flow_vjp_kernel, dim3(grid), dim3(256), lds, s, mode, blob, in, z, N, z_rows, ga, glp, glad, d_in,
+                     part != nullptr ? nullptr : dz, part);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || part == nullptr) return e;
+  hipLaunchKernelGGL(dz_reduce_kernel, dim3(1), dim3(1024), 0, s, part, grid * 4, dz);
+  return hipGetLastError();
+}
+
+hipError_t launch_goal_rows_vjp(const float* y, const float* goal, int N, int goal_rows, int G, float eps,
+                                const float* grow, float* dy, hipStream_t s) {
+  hipLaunchKernelGGL(goal_rows_vjp_kernel, dim3((N + 255) / 256), dim3(256), 0, s, y, goal, N, goal_rows, G, eps, grow, dy);
   return hipGetLastError();
 }
 

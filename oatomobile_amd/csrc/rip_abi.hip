@@ -674,6 +674,36 @@ int rip_goal_likelihood(const float* y_dev, const float* goal_dev, int N, int go
   return RIP_OK;
 }
 
+int rip_flow_vjp(rip_handle* h, int k, int mode, const float* in_dev, const float* z_dev, int N, int z_rows,
+                 const float* g_out_dev, const float* g_log_prob_dev, const float* g_logabsdet_dev, float* d_in_dev,
+                 float* dz_dev, void* workspace_dev, rip_stream_t stream) {
+  int rc = check_models(h, k, 1);
+  if (rc != RIP_OK) return rc;
+  REQUIRE(mode == RIP_FLOW_VJP_FORWARD || mode == RIP_FLOW_VJP_INVERSE, "unknown mode %d", mode);
+  REQUIRE(in_dev != nullptr && z_dev != nullptr, "NULL argument");
+  REQUIRE(N >= 0 && (z_rows == N || z_rows == 1), "z_rows=%d must be N=%d or 1", z_rows, N);
+  REQUIRE(mode == RIP_FLOW_VJP_INVERSE || g_log_prob_dev == nullptr, "g_log_prob_dev must be NULL in forward mode");
+  REQUIRE(dz_dev == nullptr || workspace_dev != nullptr || flow_vjp_workspace_bytes(N, z_rows) == 0,
+          "workspace_dev is NULL (rip_flow_vjp_workspace_bytes(%d, %d) = %zu)", N, z_rows, flow_vjp_workspace_bytes(N, z_rows));
+  if (N == 0 || (d_in_dev == nullptr && dz_dev == nullptr)) return RIP_OK;
+  ENTER(h, stream);
+  HIP_TRY(launch_flow_vjp(h->flow_w + (size_t)k * FW_SIZE, mode, in_dev, z_dev, N, z_rows, g_out_dev, g_log_prob_dev,
+                          g_logabsdet_dev, d_in_dev, dz_dev, workspace_dev, (hipStream_t)stream));
+  return RIP_OK;
+}
+
+size_t rip_flow_vjp_workspace_bytes(int N, int z_rows) { return N > 0 ? flow_vjp_workspace_bytes(N, z_rows) : 0; }
+
+int rip_goal_likelihood_vjp(const float* y_dev, const float* goal_dev, int N, int goal_rows, int G, float epsilon,
+                            const float* g_rows_dev, float* dy_dev, rip_stream_t stream) {
+  REQUIRE(y_dev != nullptr && goal_dev != nullptr && g_rows_dev != nullptr && dy_dev != nullptr, "NULL argument");
+  REQUIRE(N >= 0 && G >= 1 && (goal_rows == N || goal_rows == 1), "bad shape N=%d goal_rows=%d G=%d", N, goal_rows, G);
+  REQUIRE(epsilon > 0.f, "epsilon must be positive");
+  if (N == 0) return RIP_OK;
+  HIP_TRY(launch_goal_rows_vjp(y_dev, goal_dev, N, goal_rows, G, epsilon, g_rows_dev, dy_dev, (hipStream_t)stream));
+  return RIP_OK;
+}
+
 int rip_score(rip_handle* h, int k_begin, int k_count, const float* z_dev, const float* y_dev, const float* goal_dev,
               int B, int N, int G, float epsilon, float* S_dev, rip_stream_t stream) {
   int rc = check_models(h, k_begin, k_count);

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 import torch.distributions as D
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from oatomobile_amd import _lib
 from oatomobile_amd import arch
@@ -55,6 +56,87 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
   return t.detach().to(torch.float32).contiguous()
 
 
+def _grad_like(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+  """A kernel's fp32 gradient in the dtype and shape of the input it belongs to."""
+  return g.to(like.dtype).view(like.shape)
+
+
+class _FlowForwardFn(torch.autograd.Function):
+  """`AutoregressiveFlow._forward` as a graph node: forward = rip_flow_forward, backward = rip_flow_vjp (forward mode)."""
+
+  @staticmethod
+  def forward(ctx, flow, x, z):
+    ctx.set_materialize_grads(False)  # an unused output's cotangent reaches the kernel as NULL
+    ctx.flow = flow
+    ctx.save_for_backward(x, z)
+    return flow._launch_forward(x, z)
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gy, glad):
+    x, z = ctx.saved_tensors
+    dx, dz = ctx.flow._vjp(0, x, z, gy, None, glad, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+    return None, dx, dz
+
+
+class _FlowInverseFn(torch.autograd.Function):
+  """`AutoregressiveFlow._inverse` as a graph node: forward = rip_flow_inverse, backward = rip_flow_vjp (inverse mode)."""
+
+  @staticmethod
+  def forward(ctx, flow, y, z):
+    ctx.set_materialize_grads(False)
+    ctx.flow = flow
+    ctx.save_for_backward(y, z)
+    return flow._launch_inverse(y, z)
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gx, glp, glad):
+    y, z = ctx.saved_tensors
+    dy, dz = ctx.flow._vjp(1, y, z, gx, glp, glad, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+    return None, dy, dz
+
+
+class _GoalRowsFn(torch.autograd.Function):
+  """`ImitativeModel._goal_likelihood_rows` as a graph node: rip_goal_likelihood / rip_goal_likelihood_vjp.  The goal
+  gets no gradient (a goal that requires grad is refused before this node is built)."""
+
+  @staticmethod
+  def forward(ctx, y, goal, epsilon):
+    ctx.set_materialize_grads(False)
+    ctx.epsilon = epsilon
+    ctx.save_for_backward(y, goal)
+    return _goal_rows_launch(y, goal, epsilon)
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, grow):
+    y, goal = ctx.saved_tensors
+    if grow is None or not ctx.needs_input_grad[0]:
+      return None, None, None
+    y32, g32 = _f32c(y), _f32c(goal.to(y.device))
+    dy = torch.empty_like(y32)
+    grow = _f32c(grow)
+    with torch.cuda.device(y.device):
+      _lib.check(_lib.load().rip_goal_likelihood_vjp(_lib.ptr(y32), _lib.ptr(g32), y32.shape[0], g32.shape[0],
+                                                     g32.shape[1], ctx.epsilon, _lib.ptr(grow), _lib.ptr(dy),
+                                                     _lib.current_stream(y.device)))
+    return _grad_like(dy, y), None, None
+
+
+def _goal_rows_launch(y: torch.Tensor, goal: torch.Tensor, epsilon: float) -> torch.Tensor:
+  y, goal = _f32c(y), _f32c(goal.to(y.device))
+  n = y.shape[0]
+  rows = torch.empty(n, device=y.device, dtype=torch.float32)
+  _lib.expect_shape(y, (None, arch.T, 2), "y")
+  _lib.expect_shape(goal, (None, None, 2), "goal")
+  lib = _lib.load()
+  with torch.cuda.device(y.device):  # stateless entry point: launches on the current device
+    _lib.check(lib.rip_goal_likelihood(_lib.ptr(y), _lib.ptr(goal), n, goal.shape[0], goal.shape[1], epsilon,
+                                       _lib.ptr(rows), _lib.current_stream(y.device)))
+  return rows
+
+
 class AutoregressiveFlow(_Tree):
   """Mirror of `oatomobile.torch.networks.sequence.AutoregressiveFlow` (sequence.py:28-216):
   children `_decoder` (GRUCell weights) and `_locscale._model.{0,2}`; `_base_dist`, `forward`,
@@ -82,8 +164,31 @@ class AutoregressiveFlow(_Tree):
     return self._forward(x, z)[0]
 
   def _forward(self, x: torch.Tensor, z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """sequence.py:95-151 -> rip_flow_forward.  x [N,T,2], z [N,64] (or [1,64]) -> y [N,T,2], logabsdet [N]."""
+    """sequence.py:95-151 -> rip_flow_forward.  x [N,T,2], z [N,64] (or [1,64]) -> y [N,T,2], logabsdet [N].
+    Differentiable in x and z when grad mode is on and either requires grad (backward: rip_flow_vjp)."""
     _require_device(x, "x")
+    if self._builds_graph(x, z):
+      return _FlowForwardFn.apply(self, x, z)
+    return self._launch_forward(x, z)
+
+  def _inverse(self, y: torch.Tensor, z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """sequence.py:153-216 -> rip_flow_inverse.  Returns x [N,T,2], log_prob [N], logabsdet [N].
+    Differentiable in y and z when grad mode is on and either requires grad (backward: rip_flow_vjp)."""
+    _require_device(y, "y")
+    if self._builds_graph(y, z):
+      return _FlowInverseFn.apply(self, y, z)
+    return self._launch_inverse(y, z)
+
+  def _builds_graph(self, a: torch.Tensor, z: torch.Tensor) -> bool:
+    if not (torch.is_grad_enabled() and (a.requires_grad or z.requires_grad)):
+      return False
+    if any(p.requires_grad for p in self.parameters()):
+      raise RuntimeError("oatomobile_amd: a decoder parameter has requires_grad=True, but gradients do not reach model "
+                         "parameters (only the flow's inputs x / y and z are differentiable); call "
+                         "`requires_grad_(False)` on the model, or run this call under torch.no_grad()")
+    return True
+
+  def _launch_forward(self, x: torch.Tensor, z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     h = self._owner._handle()
     x, z = _f32c(x), _f32c(z)
     n = x.shape[0]
@@ -94,9 +199,7 @@ class AutoregressiveFlow(_Tree):
                                     h.stream()))
     return y, lad
 
-  def _inverse(self, y: torch.Tensor, z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """sequence.py:153-216 -> rip_flow_inverse.  Returns x [N,T,2], log_prob [N], logabsdet [N]."""
-    _require_device(y, "y")
+  def _launch_inverse(self, y: torch.Tensor, z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     h = self._owner._handle()
     y, z = _f32c(y), _f32c(z)
     n = y.shape[0]
@@ -107,6 +210,26 @@ class AutoregressiveFlow(_Tree):
     _lib.check(lib.rip_flow_inverse(h.raw, 0, _lib.ptr(y), _lib.ptr(z), n, z.shape[0], _lib.ptr(x), _lib.ptr(lp),
                                     _lib.ptr(lad), h.stream()))
     return x, lp, lad
+
+  def _vjp(self, mode: int, inp: torch.Tensor, z: torch.Tensor, g_out, g_logp, g_lad, want_in: bool,
+           want_z: bool) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """rip_flow_vjp of `_forward` (mode 0: inp = x, g_out = dL/dy) or `_inverse` (mode 1: inp = y, g_out = dL/dx, g_logp
+    = dL/dlog_prob); None cotangents are zero.  Returns (dL/dinp, dL/dz) in the inputs' dtypes and shapes."""
+    h = self._owner._handle()
+    inp32, z32 = _f32c(inp), _f32c(z)
+    n, z_rows = inp32.shape[0], z32.shape[0]
+    d_in = torch.empty_like(inp32) if want_in else None
+    dz = (torch.zeros_like(z32) if n == 0 else torch.empty_like(z32)) if want_z else None
+    lib = _lib.load()
+    ws = None
+    if want_z:
+      ws_bytes = lib.rip_flow_vjp_workspace_bytes(n, z_rows)
+      if ws_bytes:
+        ws = torch.empty(ws_bytes // 4, device=inp32.device, dtype=torch.float32)
+    cot = [None if g is None else _f32c(g) for g in (g_out, g_logp, g_lad)]
+    _lib.check(lib.rip_flow_vjp(h.raw, 0, mode, _lib.ptr(inp32), _lib.ptr(z32), n, z_rows, *[_lib.ptr(g) for g in cot],
+                                _lib.ptr(d_in), _lib.ptr(dz), _lib.ptr(ws), h.stream()))
+    return (_grad_like(d_in, inp) if want_in else None), (_grad_like(dz, z) if want_z else None)
 
 
 class ImitativeModel(nn.Module):
@@ -232,18 +355,16 @@ class ImitativeModel(nn.Module):
     return self._goal_likelihood_rows(y, goal, **hyperparams).mean(dim=0)
 
   def _goal_likelihood_rows(self, y: torch.Tensor, goal: torch.Tensor, **hyperparams) -> torch.Tensor:
+    """Per-row goal log-likelihood [N]; differentiable in y when grad mode is on and y requires grad (backward:
+    rip_goal_likelihood_vjp).  A goal that requires grad is refused: no gradient reaches the goal."""
     _require_device(y, "y")
     epsilon = float(hyperparams.get("epsilon", 1.0))
-    y, goal = _f32c(y), _f32c(goal.to(y.device))
-    n = y.shape[0]
-    rows = torch.empty(n, device=y.device, dtype=torch.float32)
-    _lib.expect_shape(y, (None, arch.T, 2), "y")
-    _lib.expect_shape(goal, (None, None, 2), "goal")
-    lib = _lib.load()
-    with torch.cuda.device(y.device):  # stateless entry point: launches on the current device
-      _lib.check(lib.rip_goal_likelihood(_lib.ptr(y), _lib.ptr(goal), n, goal.shape[0], goal.shape[1], epsilon,
-                                         _lib.ptr(rows), _lib.current_stream(y.device)))
-    return rows
+    if torch.is_grad_enabled() and (y.requires_grad or goal.requires_grad):
+      if goal.requires_grad:
+        raise RuntimeError("oatomobile_amd: `goal` requires grad, but gradients do not reach goals (only y is "
+                           "differentiable here); pass `goal.detach()`")
+      return _GoalRowsFn.apply(y, goal, epsilon)
+    return _goal_rows_launch(y, goal, epsilon)
 
   def _params(self, **context: torch.Tensor) -> torch.Tensor:
     """Contextual parameters z [B, 64] (dim/model.py:173-219 -> rip_encode)."""

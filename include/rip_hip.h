@@ -277,6 +277,35 @@ int rip_act(rip_handle* h, const float* lidar_dev, int channels_last, int H, int
             float epsilon, int enc_dtype, float* plan_dev, float* loss_best_dev, double* plan_interp_dev,
             rip_stream_t stream);
 
+/* Ensemble disagreement of given trajectories — the "identify" statistic of RIP (Filos et al. 2020: the
+ * variance over the ensemble members of log q_k(y | x)) — for all K loaded models, one launch:
+ *   z_dev [K,B,64] (rip_encode / rip_encode_raw of the K members), y_dev [B,M,4,2]: M trajectories per observation
+ *   (M = 1: "the plan");
+ *   q_dev [K,B,M] = log_prob_k - logabsdet_k of AutoregressiveFlow._inverse (sequence.py:153-216): the imitation prior,
+ *     bit for bit what rip_score writes for the same inputs without a goal (NULL to skip);
+ *   stats_dev [B,M,RIP_STAT_SLOTS] = mean, population variance, min and max of q over the K members (NULL to skip).
+ * The goal term of the plan loss is left out: it depends on y and the goal only, so it is the same for every member and
+ * cannot change the variance.  The reduction runs inside the launch in model order 0..K-1, the variance in two fp32
+ * passes (the mean, then the squared deviations), without atomics: the same bits on every run; K = 1 gives variance 0
+ * and mean = min = max = q.  RIP_EINVAL (nothing is launched) for a NULL handle, z_dev or y_dev, B < 1, M < 1, or both
+ * outputs NULL. */
+#define RIP_STAT_MEAN 0
+#define RIP_STAT_VARIANCE 1
+#define RIP_STAT_MIN 2
+#define RIP_STAT_MAX 3
+#define RIP_STAT_SLOTS 4
+int rip_plan_stats(rip_handle* h, const float* z_dev, const float* y_dev, int B, int M, float* q_dev, float* stats_dev,
+                   rip_stream_t stream);
+
+/* rip_act, then the statistics of the WINNING plan on the z it just encoded, on the same stream: q_dev [K,B] and
+ * stats_dev [B,RIP_STAT_SLOTS] as rip_plan_stats with M = 1 (either may be NULL).  With both NULL this is exactly
+ * rip_act: the same launches.  The statistics need the [B,4,2] plan: when plan_dev is NULL (only the interpolated plan
+ * was asked for) it is kept in handle scratch.  Plan, loss and interpolated plan are the bits rip_act writes. */
+int rip_act_stats(rip_handle* h, const float* lidar_dev, int channels_last, int H, int W, const float* vec_dev,
+                  const float* goal_dev, const float* x0_dev, int B, int N, int G, int algorithm, int num_steps, float lr,
+                  float epsilon, int enc_dtype, float* plan_dev, float* loss_best_dev, double* plan_interp_dev,
+                  float* q_dev, float* stats_dev, rip_stream_t stream);
+
 /* N3 — the DIM training step, oatomobile/baselines/torch/dim/train.py:175-213:
  *   z = model._params(...) in TRAIN mode (MobileNetV2 BatchNorm on batch statistics with the running-stat update,
  *   Dropout before the classifier), _, log_prob, logabsdet = decoder._inverse(y, z),

@@ -5,6 +5,7 @@ path in scope: `ImitativeModel`, `RIPAgent`, `DIMAgent`.
 """
 
 from oatomobile_amd.agents import DIMAgent
+from oatomobile_amd.agents import PlanStats
 from oatomobile_amd.agents import RIPAgent
 from oatomobile_amd.agents import SetPointAgent
 from oatomobile_amd.model import ImitativeModel
@@ -12,9 +13,10 @@ from oatomobile_amd.model import transform_visual
 
 from oatomobile_amd.cil import BehaviouralModel
 from oatomobile_amd.cil import CILAgent
+from oatomobile_amd.detection import detection_auroc
 from oatomobile_amd.lidar import lidar_to_bev
 from oatomobile_amd.train import CILTrainer
 from oatomobile_amd.train import DIMTrainer
 
 __all__ = ["ImitativeModel", "RIPAgent", "DIMAgent", "SetPointAgent", "transform_visual", "lidar_to_bev",
-           "BehaviouralModel", "CILAgent", "DIMTrainer", "CILTrainer"]
+           "BehaviouralModel", "CILAgent", "DIMTrainer", "CILTrainer", "PlanStats", "detection_auroc"]

@@ -61,6 +61,11 @@ SIGNATURES = [
         c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
         c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p
     ]),
+    ("rip_plan_stats", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("rip_act_stats", c_int, [
+        c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+        c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p
+    ]),
     ("rip_interpolate_plans", c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     ("rip_search_plan", c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     ("rip_search_stats", c_int, [c_void_p, c_void_p, c_int]),
@@ -100,6 +105,7 @@ OPT_SEARCH_KERNEL, OPT_ENCODER_FUSED, OPT_SEARCH_REGROUP, OPT_ENCODER_MEGA, OPT_
 OPT_ENCODER_VARIANT, OPT_KERNEL_LOG = 5, 6
 ENC_VAR_IRB_ROUND3, ENC_VAR_FRONT_ROUND3, ENC_VAR_ROWS_F5_7, ENC_VAR_F17_LAYERWISE = 1, 2, 4, 8
 ENC_VAR_FP32_LAYERWISE = 16  # fp32 encoder without the split-f16 tile blocks (encoder_split_tile.hip)
+STAT_MEAN, STAT_VARIANCE, STAT_MIN, STAT_MAX, STAT_SLOTS = 0, 1, 2, 3, 4  # RIP_STAT_* of include/rip_hip.h
 SEARCH_KERNELS = {"auto": 0, "chain": 1, "phase": 3, "split": 4, "pair": 5}  # "pair": split-f16, paired workgroup shape forced
 
 

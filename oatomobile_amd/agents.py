@@ -10,7 +10,7 @@ setpoint/target-speed pair the PID would consume.
 
 import copy
 import os
-from typing import Any, Mapping, Optional, Sequence
+from typing import Any, Mapping, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -21,6 +21,23 @@ from oatomobile_amd.model import ImitativeModel
 
 SIMULATOR_FPS = 20  # base.py:31
 PLAN_ROWS = 30  # rows of the interpolated plan (rip/agent.py:141-151; RIP_PLAN_ROWS in include/rip_hip.h)
+
+
+class PlanStats(NamedTuple):
+  """Ensemble disagreement of trajectories (`rip_plan_stats`): `q` [K,B] or [K,B,M] = log q_k(y | x) of every member
+  (the imitation prior, log_prob - logabsdet, without the goal term: it is the same for every member), and its `mean`,
+  population `variance`, `min` and `max` over the K members, [B] or [B,M].  Device tensors from the batch entry points,
+  numpy arrays in `RIPAgent.last_stats`."""
+  q: Any
+  mean: Any
+  variance: Any
+  min: Any
+  max: Any
+
+
+def _plan_stats(q, st) -> PlanStats:
+  """(q [K,...], stats [...,4]) -> PlanStats of views."""
+  return PlanStats(q, st[..., _lib.STAT_MEAN], st[..., _lib.STAT_VARIANCE], st[..., _lib.STAT_MIN], st[..., _lib.STAT_MAX])
 
 
 def interpolate_plan(plan: np.ndarray, player_future_length: int = 40) -> np.ndarray:
@@ -166,6 +183,10 @@ class RIPAgent(SetPointAgent):
     graph: `__call__` (one observation per call, the reference's usage) replays ONE captured hipGraph per call
       (H2D of the observation from pinned staging, transform, K encoders, search, D2H of the plan) instead of
       ~60 eager launches.  Same kernels, same results.
+    stats: `__call__` also computes the ensemble disagreement of the plan it returns (`rip_act_stats`: one more kernel
+      behind the search, its K + 4 floats in the same D2H copy as the plan) and leaves it in `last_stats`, a `PlanStats`
+      of numpy arrays (q [K,1]; mean, variance, min, max [1]); None before the first call and with `stats=False`
+      (default: the pipeline of a call is then unchanged).  The batch entry points take `return_stats=` per call.
 
   The agent uploads a snapshot of every model's weights; the snapshot is refreshed automatically when a model's
   `load_state_dict()` / `refresh()` ran since (the reference agent reads the live module weights).
@@ -174,7 +195,8 @@ class RIPAgent(SetPointAgent):
   def __init__(self, environment: Any = None, *, algorithm: str, models: Sequence[ImitativeModel],
                num_candidates: int = 1, num_steps: int = 10, lr: float = 1e-1, epsilon: float = 1.0, seed: int = 0,
                max_batch: int = 1, device: Optional[torch.device] = None, search_kernel: str = "auto",
-               fused_encoder: Optional[int] = None, encoder_dtype: str = "fp32", graph: bool = True, **kwargs) -> None:
+               fused_encoder: Optional[int] = None, encoder_dtype: str = "fp32", graph: bool = True, stats: bool = False,
+               **kwargs) -> None:
     assert algorithm in ("WCM", "MA", "BCM")  # rip/agent.py:43
     self._algorithm = algorithm
     super().__init__(environment=environment, **kwargs)
@@ -190,7 +212,9 @@ class RIPAgent(SetPointAgent):
     self._enc_dtype = _lib.ENC_DTYPES[encoder_dtype]
     self._twin_args = dict(algorithm=algorithm, num_candidates=num_candidates, num_steps=num_steps, lr=lr, epsilon=epsilon,
                            seed=seed, max_batch=max_batch, search_kernel=search_kernel, fused_encoder=fused_encoder,
-                           encoder_dtype=encoder_dtype, graph=graph, **kwargs)
+                           encoder_dtype=encoder_dtype, graph=graph, stats=stats, **kwargs)
+    self._stats = bool(stats)
+    self.last_stats: Optional[PlanStats] = None
     self._handle = _lib.Handle(len(self._models), self._in_channels, self._max_batch, self._device.index,
                                max_candidates=self._num_candidates)
     self._versions = [None] * len(self._models)
@@ -242,31 +266,69 @@ class RIPAgent(SetPointAgent):
       self._x0_cache[batch] = self._x0_rows.unsqueeze(0).expand(batch, -1, -1, -1).contiguous()
     return self._x0_cache[batch]
 
-  def _check_batch(self, lidar: torch.Tensor, vec: torch.Tensor, goal: torch.Tensor) -> None:
-    """The C ABI takes raw pointers: dtype, device and shape are enforced here (ValueError / RuntimeError)."""
-    for name, t in (("lidar", lidar), ("vec", vec), ("goal", goal)):
+  def _check_batch(self, lidar: torch.Tensor, vec: torch.Tensor, goal: Optional[torch.Tensor], y: Optional[torch.Tensor] = None,
+                   what: str = "plan_batch") -> None:
+    """The C ABI takes raw pointers: dtype, device and shape are enforced here (ValueError / RuntimeError).  `goal`
+    [B,G,2] (plan_batch) or `y` [B,4,2] / [B,M,4,2] (score_trajectories) is the third input."""
+    third = ("goal", goal) if y is None else ("y", y)
+    for name, t in (("lidar", lidar), ("vec", vec), third):
       if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self._device:
-        raise RuntimeError("plan_batch: `%s` must be a tensor on %s (got %s)" %
-                           (name, self._device, getattr(t, "device", type(t))))
+        raise RuntimeError("%s: `%s` must be a tensor on %s (got %s)" %
+                           (what, name, self._device, getattr(t, "device", type(t))))
       if t.dtype != torch.float32:
-        raise ValueError("plan_batch: `%s` must be float32, got %s" % (name, t.dtype))
+        raise ValueError("%s: `%s` must be float32, got %s" % (what, name, t.dtype))
     _lib.expect_shape(lidar, (None, None, None, self._in_channels), "lidar")
     b = lidar.shape[0]
     if b < 1 or b > self._max_batch or lidar.shape[1] < 1 or lidar.shape[2] < 1:
-      raise ValueError("plan_batch: lidar %s: batch must be in [1, max_batch=%d], H, W >= 1" %
-                       (tuple(lidar.shape), self._max_batch))
+      raise ValueError("%s: lidar %s: batch must be in [1, max_batch=%d], H, W >= 1" %
+                       (what, tuple(lidar.shape), self._max_batch))
     _lib.expect_shape(vec, (b, 5), "vec")
+    if y is not None:
+      _lib.expect_shape(y, (b, arch.T, 2) if y.dim() == 3 else (b, None, arch.T, 2), "y")
+      if y.shape[1] < 1:
+        raise ValueError("%s: y needs at least one trajectory per observation" % what)
+      return
     _lib.expect_shape(goal, (b, None, 2), "goal")
     if goal.shape[1] < 1:
       raise ValueError("plan_batch: goal needs at least one waypoint")
 
+  def _stats_out(self, b: int, m: Optional[int] = None):
+    """Fresh (q [K,B] or [K,B,M], stats [B,4] or [B,M,4]) outputs of a statistics launch."""
+    K, mid = len(self._models), (() if m is None else (m,))
+    return (torch.empty((K, b) + mid, device=self._device, dtype=torch.float32),
+            torch.empty((b,) + mid + (_lib.STAT_SLOTS,), device=self._device, dtype=torch.float32))
+
+  def score_trajectories(self, lidar: torch.Tensor, vec: torch.Tensor, y: torch.Tensor) -> PlanStats:
+    """Ensemble disagreement of GIVEN trajectories: lidar [B,H,W,C], vec [B,5] as `plan_batch`, y [B,4,2] or [B,M,4,2]
+    (M trajectories per observation, e.g. the expert's future or a set of candidates) -> `PlanStats` of device tensors
+    (q [K,B] / [K,B,M]; mean, variance, min, max [B] / [B,M]).  One `rip_encode_raw` for the K members, then one
+    `rip_plan_stats` launch."""
+    self._check_batch(lidar, vec, None, y=y, what="score_trajectories")
+    if self._sync_weights():
+      self._online = {}
+    lidar, vec, y = lidar.contiguous(), vec.contiguous(), y.contiguous()
+    b, K = lidar.shape[0], len(self._models)
+    m = None if y.dim() == 3 else y.shape[1]
+    z = torch.empty(K, b, 64, device=self._device, dtype=torch.float32)
+    q, st = self._stats_out(b, m)
+    lib, stream = _lib.load(), self._handle.stream()
+    self._eager_pending = True
+    _lib.check(lib.rip_encode_raw(self._handle.raw, _lib.ptr(lidar), 1, lidar.shape[1], lidar.shape[2], _lib.ptr(vec), b, 0, K,
+                                  self._enc_dtype, _lib.ptr(z), stream))
+    _lib.check(lib.rip_plan_stats(self._handle.raw, _lib.ptr(z), _lib.ptr(y), b, 1 if m is None else m, _lib.ptr(q),
+                                  _lib.ptr(st), stream))
+    return _plan_stats(q, st)
+
   def plan_batch(self, lidar: torch.Tensor, vec: torch.Tensor, goal: torch.Tensor,
-                 return_loss: bool = False, interpolate: bool = False, out: Optional[torch.Tensor] = None):
+                 return_loss: bool = False, interpolate: bool = False, out: Optional[torch.Tensor] = None,
+                 return_stats: bool = False):
     """Device-resident batched planning: lidar [B,H,W,C] (sensor layout; 200 x 200 from CARLA), vec [B,5],
     goal [B,G,2] -> plans [B,4,2] (and best losses [B,N]).  One rip_act call (transform + K encoders + search).
     `interpolate=True` returns what `__call__` returns per observation instead — the [B,30,3] float64 plans of
     rip/agent.py:141-151 — computed by the candidate-selection kernel (R11 on the device, bit-identical to the
-    reference's scipy arithmetic); `out` = a caller-owned result tensor to write into."""
+    reference's scipy arithmetic); `out` = a caller-owned result tensor to write into.  `return_stats=True` appends
+    the ensemble disagreement of the returned plans, a `PlanStats` of device tensors (q [K,B]; mean, variance, min,
+    max [B]), to the returned tuple: one more kernel behind the search (`rip_act_stats`), same plans and losses."""
     self._check_batch(lidar, vec, goal)
     if self._sync_weights():
       self._online = {}
@@ -278,19 +340,23 @@ class RIPAgent(SetPointAgent):
     elif tuple(out.shape) != shape or out.dtype != dtype or out.device != self._device or not out.is_contiguous():
       raise ValueError("plan_batch: `out` must be a contiguous %s tensor of shape %s on %s" % (dtype, shape, self._device))
     loss = torch.empty(b, self._num_candidates, device=self._device, dtype=torch.float32) if return_loss else None
+    q, st = self._stats_out(b) if return_stats else (None, None)
     self._eager_pending = True
     if interpolate:
-      self._launch_act(lidar, vec, goal, None, loss, out)
+      self._launch_act(lidar, vec, goal, None, loss, out, q, st)
     else:
-      self._launch_act(lidar, vec, goal, out, loss)
+      self._launch_act(lidar, vec, goal, out, loss, None, q, st)
+    if return_stats:
+      return (out, loss, _plan_stats(q, st)) if return_loss else (out, _plan_stats(q, st))
     return (out, loss) if return_loss else out
 
   def plan_batch_coded(self, codes: torch.Tensor, lut: torch.Tensor, vec: torch.Tensor, goal: torch.Tensor,
-                       interpolate: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       interpolate: bool = False, out: Optional[torch.Tensor] = None, return_stats: bool = False):
     """`plan_batch` on a CODED BEV (the replay cache, `replay.PackedCache`): codes [B,H,W,C] uint8 indices into
     lut [256] float32 — the distinct float32 values of the BEV the cache was packed from — vec [B,5], goal [B,G,2].
     The table is applied inside the transform kernel (`rip_encode_raw_u8`), so the plans are bit-identical to
-    `plan_batch` on the float32 BEV while a quarter of its bytes cross PCIe and HBM."""
+    `plan_batch` on the float32 BEV while a quarter of its bytes cross PCIe and HBM.  `return_stats=True` returns
+    `(plans, PlanStats)` as `plan_batch` does (`rip_plan_stats` on the z and the plans of this call)."""
     dev = self._device
     if not (isinstance(codes, torch.Tensor) and codes.is_cuda and codes.device == dev and codes.dtype == torch.uint8):
       raise ValueError("plan_batch_coded: `codes` must be a uint8 tensor on %s" % (dev,))
@@ -324,11 +390,22 @@ class RIPAgent(SetPointAgent):
                               None, None, None, None, None, None, st))
     if interpolate:
       _lib.check(lib.rip_interpolate_plans(_lib.ptr(plan4), b, _lib.ptr(out, torch.float64), st))
+    if return_stats:
+      q, stats = self._stats_out(b)
+      _lib.check(lib.rip_plan_stats(self._handle.raw, _lib.ptr(z), _lib.ptr(target), b, 1, _lib.ptr(q), _lib.ptr(stats), st))
+      return out, _plan_stats(q, stats)
     return out
 
-  def _launch_act(self, lidar, vec, goal, plan, loss, plan_interp=None) -> None:
+  def _launch_act(self, lidar, vec, goal, plan, loss, plan_interp=None, q=None, stats=None) -> None:
     b = lidar.shape[0]
     lib = _lib.load()
+    if q is not None or stats is not None:
+      _lib.check(lib.rip_act_stats(self._handle.raw, _lib.ptr(lidar), 1, lidar.shape[1], lidar.shape[2], _lib.ptr(vec),
+                                   _lib.ptr(goal), _lib.ptr(self._x0(b)), b, self._num_candidates, goal.shape[1],
+                                   _lib.ALGORITHMS[self._algorithm], self._num_steps, self._lr, self._epsilon,
+                                   self._enc_dtype, _lib.ptr(plan), _lib.ptr(loss), _lib.ptr(plan_interp, torch.float64),
+                                   _lib.ptr(q), _lib.ptr(stats), self._handle.stream()))
+      return
     _lib.check(lib.rip_act(self._handle.raw, _lib.ptr(lidar), 1, lidar.shape[1], lidar.shape[2], _lib.ptr(vec),
                            _lib.ptr(goal), _lib.ptr(self._x0(b)), b, self._num_candidates, goal.shape[1],
                            _lib.ALGORITHMS[self._algorithm], self._num_steps, self._lr, self._epsilon, self._enc_dtype,
@@ -353,19 +430,36 @@ class RIPAgent(SetPointAgent):
 
     lidar_h, vec_h, goal_h = views(obs_h)
     lidar_d, vec_d, goal_d = views(obs_d)
+    if self._stats:
+      # (plan [1,30,3] float64 | stats [1,4] | q [K,1]) in ONE device buffer and ONE pinned buffer: the K + 4 floats of
+      # the statistics ride in the plan's D2H copy node (720 bytes of plan keep the 16-byte statistics row aligned)
+      K, nb, ns = len(self._models), PLAN_ROWS * 3 * 8, 4 * _lib.STAT_SLOTS
+
+      def outs(buf):
+        return (buf[:nb].view(torch.float64).view(1, PLAN_ROWS, 3), buf[nb + ns:].view(torch.float32).view(K, 1),
+                buf[nb:nb + ns].view(torch.float32).view(1, _lib.STAT_SLOTS))
+
+      out_h = torch.zeros(nb + 4 * (K + _lib.STAT_SLOTS), dtype=torch.uint8).pin_memory()
+      out_d = torch.zeros(nb + 4 * (K + _lib.STAT_SLOTS), dtype=torch.uint8, device=dev)
+      plan_h, q_h, stat_h = outs(out_h)
+      plan_d, q_d, stat_d = outs(out_d)
+    else:
+      plan_h = out_h = torch.empty(1, PLAN_ROWS, 3, dtype=torch.float64).pin_memory()
+      plan_d = out_d = torch.empty(1, PLAN_ROWS, 3, dtype=torch.float64, device=dev)
+      q_h = stat_h = q_d = stat_d = None
     st = dict(
         obs_h=obs_h, obs_d=obs_d, lidar_h=lidar_h, vec_h=vec_h, goal_h=goal_h,
-        plan_h=torch.empty(1, PLAN_ROWS, 3, dtype=torch.float64).pin_memory(),
+        plan_h=plan_h,
         lidar_d=lidar_d, vec_d=vec_d, goal_d=goal_d,
-        plan_d=torch.empty(1, PLAN_ROWS, 3, dtype=torch.float64, device=dev),
+        plan_d=plan_d, out_h=out_h, out_d=out_d, q_h=q_h, stat_h=stat_h, q_d=q_d, stat_d=stat_d,
         stream=torch.cuda.Stream(device=dev), graph=None)
     st["lidar_np"], st["vec_np"], st["goal_np"] = st["lidar_h"].numpy(), st["vec_h"].numpy(), st["goal_h"].numpy()
     self._x0(1)
 
     def pipeline():
       st["obs_d"].copy_(st["obs_h"], non_blocking=True)
-      self._launch_act(st["lidar_d"], st["vec_d"], st["goal_d"], None, None, st["plan_d"])  # R2..R11
-      st["plan_h"].copy_(st["plan_d"], non_blocking=True)  # rip/agent.py:139 (720 bytes: the interpolated plan)
+      self._launch_act(st["lidar_d"], st["vec_d"], st["goal_d"], None, None, st["plan_d"], st["q_d"], st["stat_d"])  # R2..R11
+      st["out_h"].copy_(st["out_d"], non_blocking=True)  # rip/agent.py:139 (720 bytes: the interpolated plan)
 
     st["pipeline"] = pipeline
     if self._use_graph:
@@ -444,7 +538,9 @@ class RIPAgent(SetPointAgent):
       if _retry:
         raise RuntimeError("the encoder reported a failure again after falling back to the layer-wise launches")
       self._online = {}
-      return self.__call__(observation, _retry=True)
+      return self.__call__(observation, _retry=True)  # (refreshes `last_stats` as well)
+    if self._stats:
+      self.last_stats = _plan_stats(st["q_h"].numpy().copy(), st["stat_h"].numpy().copy())
     return st["plan_h"].numpy()[0].copy()  # [30, 3] float64: R11 ran in the selection kernel
 
 

@@ -106,6 +106,12 @@ hipError_t launch_goal_rows_vjp(const float* y, const float* goal, int N, int go
                                 const float* grow, float* dy, hipStream_t s);
 hipError_t launch_score(const float* flow_w, int k0, int K, const float* z, const float* y, const float* goal, int B,
                         int N, int G, float eps, float* S, hipStream_t s);
+// Ensemble disagreement of trajectories y [B][M][8] under the K models of flow_w (z [K][B][64]), one launch:
+// q [K][B][M] = log_prob_k - logabsdet_k (launch_score's values without a goal: the goal term depends on y and the goal
+// only, is the same for every member and cannot change the variance) and stats [B][M][4] = (mean, population variance,
+// min, max) over the members, reduced in model order without atomics.  Either output may be nullptr.  K <= MAX_MODELS.
+hipError_t launch_ensemble_stats(const float* flow_w, int K, const float* z, const float* y, int B, int M, float* q,
+                                 float* stats, hipStream_t s);
 hipError_t launch_search(const SearchArgs& a, hipStream_t s);
 hipError_t launch_select_best(const float* plans, const float* loss_best, int B, int N, float* plan, int32_t* best,
                               double* interp /*[B][30][3] or nullptr*/, hipStream_t s);

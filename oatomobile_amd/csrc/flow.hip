@@ -569,6 +569,83 @@ __global__ __launch_bounds__(256) void score_kernel(const float* __restrict__ fl
   }
 }
 
+// Ensemble disagreement of given trajectories (the "identify" statistic of RIP): q[k,b,m] = log_prob_k(y[b,m]) -
+// logabsdet_k(y[b,m]), the imitation prior of member k (AutoregressiveFlow._inverse, sequence.py:153-216) — score_kernel's
+// expression without a goal, hence its bits — and stats[b,m,:] = (mean, population variance, min, max) of q over the K
+// members.  The goal term of the plan loss is left out: it depends on y and the goal only, so it is the same for every
+// member and cannot change the variance.
+// One workgroup of up to four waves (one per SIMD: a wave that holds a member's FlowRegs needs the SIMD's whole register
+// file) walks a contiguous span of at most STATS_ROWS (b, m) rows, so a prefix is reused over the M trajectories of an
+// observation.  K <= 4: wave k keeps member k's weights for the whole launch.  K > 4: two passes over the span, the
+// waves loading members [pass * NW, pass * NW + NW).  The K values of a row meet in LDS; after the last pass thread i
+// reduces row i in model order 0..K-1, in two fp32 passes (the mean, then the squared deviations): no atomics, the same
+// bits on every run; K = 1 gives variance 0 and mean = min = max = q.
+constexpr int STATS_ROWS = 64;
+__global__ __launch_bounds__(256) void ensemble_stats_kernel(const float* __restrict__ flow_w, int K,
+                                                             const float* __restrict__ z, const float* __restrict__ y,
+                                                             int B, int M, int rows_per_wg, float* __restrict__ q,
+                                                             float* __restrict__ stats) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  float* w1 = smem + wave * W1_LDS;
+  float* my_in = smem + nw * W1_LDS + wave * 8;
+  float* qs = smem + nw * (W1_LDS + 8);  // [rows_per_wg][MAX_MODELS]
+  const float* w1row = w1 + (lane & 31) * W1_STRIDE;
+  const int rows = B * M;
+  const int r0 = blockIdx.x * rows_per_wg;
+  const int r1 = r0 + rows_per_wg < rows ? r0 + rows_per_wg : rows;
+  FlowRegs W;
+#pragma unroll 1
+  for (int k0 = 0; k0 < K; k0 += nw) {
+    const int k = k0 + wave;
+    if (k < K) {  // wave-uniform
+      const float* blob = flow_w + (size_t)k * FW_SIZE;
+      stage_w1(w1, blob, lane, 64);  // this wave's rows only: read by no other wave
+      load_flow_regs(W, blob, lane);
+    }
+    __syncthreads();
+    if (k < K) {
+      Prefix pre;
+      int pre_b = -1;
+#pragma unroll 1
+      for (int row = r0; row < r1; ++row) {
+        const int b = row / M;
+        if (lane < 8) my_in[lane] = y[(size_t)row * 8 + lane];
+        if (b != pre_b) {
+          pre = chain_prefix(W, w1row, z[((size_t)k * B + b) * 64 + lane]);
+          pre_b = b;
+        }
+        __builtin_amdgcn_wave_barrier();
+        const ChainOut o = chain_forward<false>(MODE_INV, W, w1row, pre, my_in, nullptr, nullptr, lane);
+        const float s = (-0.5f * o.sq - 4.0f * LOG_2PI) - o.lad;
+        if (lane == 0) {
+          qs[(row - r0) * MAX_MODELS + k] = s;
+          if (q != nullptr) q[(size_t)k * rows + row] = s;
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+    __syncthreads();
+  }
+  if (stats == nullptr) return;
+  for (int i = tid; i < r1 - r0; i += blockDim.x) {
+    const float* v = qs + i * MAX_MODELS;
+    float sum = 0.f, lo = v[0], hi = v[0];
+    for (int j = 0; j < K; ++j) {
+      sum += v[j];
+      lo = fminf(lo, v[j]);
+      hi = fmaxf(hi, v[j]);
+    }
+    const float mean = sum / (float)K;
+    float dev2 = 0.f;
+    for (int j = 0; j < K; ++j) {
+      const float d = v[j] - mean;
+      dev2 = fmaf(d, d, dev2);
+    }
+    *reinterpret_cast<float4*>(stats + (size_t)(r0 + i) * 4) = make_float4(mean, dev2 / (float)K, lo, hi);
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // fused plan search: one workgroup per (observation b, candidate n); NW waves share the K models
 // ------------------------------------------------------------------------------------------
@@ -1709,6 +1786,20 @@ hipError_t launch_score(const float* flow_w, int k0, int K, const float* z, cons
   const size_t lds = (W1_LDS + 4 * 8) * sizeof(float);
   hipLaunchKernelGGL(score_kernel, dim3(rows_grid(B * N), K), dim3(256), lds, s, flow_w, k0, z, y, goal, B, N, G, eps,
                      S);
+  return hipGetLastError();
+}
+
+hipError_t launch_ensemble_stats(const float* flow_w, int K, const float* z, const float* y, int B, int M, float* q,
+                                 float* stats, hipStream_t s) {
+  // rows per workgroup: at least two (its weight sets are loaded once per workgroup), then what spreads the rows over 512
+  // workgroups, at most STATS_ROWS (the LDS table of a span); waves: K members over ceil(K / 4) passes
+  const int rows = B * M;
+  int per = (rows + 511) / 512;
+  per = per < 2 ? 2 : (per > STATS_ROWS ? STATS_ROWS : per);
+  const int passes = (K + 3) / 4, nw = (K + passes - 1) / passes;
+  const size_t lds = (size_t)(nw * (W1_LDS + 8) + per * MAX_MODELS) * sizeof(float);
+  hipLaunchKernelGGL(ensemble_stats_kernel, dim3((rows + per - 1) / per), dim3(nw * 64), lds, s, flow_w, K, z, y, B, M,
+                     per, q, stats);
   return hipGetLastError();
 }
 

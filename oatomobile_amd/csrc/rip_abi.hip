@@ -58,6 +58,7 @@ struct rip_handle {
   float* z = nullptr;          // [K][max_batch][64]
   float* plans = nullptr;      // [max_batch][max_candidates][8]
   float* loss_best = nullptr;  // [max_batch][max_candidates]
+  float* stat_plan = nullptr;  // [max_batch][8] the winning plans of rip_act_stats when the caller takes only the interpolated ones
   float* trace_loss = nullptr; // [RIP_MAX_STEPS][max_batch]   (ImitativeModel.forward)
   float* trace_x = nullptr;    // [RIP_MAX_STEPS][max_batch][8]
   unsigned long long* stats = nullptr;  // [1] executed inverse-pass adjoints of the phase-sequential kernels (rip_search_stats)
@@ -267,6 +268,7 @@ int rip_create(rip_handle** out, int K, int in_channels, int max_batch, int max_
   // plan-search scratch: nothing is (re)allocated after this point (include/rip_hip.h: calls never synchronise)
   ALLOC(h->plans, (size_t)max_batch * max_candidates * 8);
   ALLOC(h->loss_best, (size_t)max_batch * max_candidates);
+  ALLOC(h->stat_plan, (size_t)max_batch * 8);
   ALLOC(h->trace_loss, (size_t)RIP_MAX_STEPS * max_batch);
   ALLOC(h->trace_x, (size_t)RIP_MAX_STEPS * max_batch * 8);
   {
@@ -312,7 +314,7 @@ int rip_destroy(rip_handle* h) {
   if (h->mega_sync != nullptr) (void)hipFree(h->mega_sync);
   if (h->mega_arena != nullptr) (void)hipFree(h->mega_arena);
   float* ptrs[] = {h->enc_w, h->enc_wt, reinterpret_cast<float*>(h->enc_wh), reinterpret_cast<float*>(h->enc_wc), reinterpret_cast<float*>(h->enc_wr), h->flow_w, h->mfma_w, reinterpret_cast<float*>(h->split_w), h->bufs[0], h->bufs[1], h->bufs[2], h->bufs[3], h->visual,
-                   h->z,     h->plans,  h->loss_best, h->trace_loss, h->trace_x, reinterpret_cast<float*>(h->stats)};
+                   h->z,     h->plans,  h->loss_best, h->trace_loss, h->trace_x, reinterpret_cast<float*>(h->stats), h->stat_plan};
   for (float* p : ptrs)
     if (p != nullptr) (void)hipFree(p);
   delete h;
@@ -953,6 +955,42 @@ int rip_act(rip_handle* h, const float* lidar_dev, int channels_last, int H, int
   // h->z is [K][B][64] because rip_encode packs by the B it was given
   return search_impl(h, h->z, goal_dev, x0_dev, B, N, G, algorithm, num_steps, lr, epsilon, plan_dev, nullptr,
                      loss_best_dev, nullptr, nullptr, nullptr, nullptr, plan_interp_dev, stream);
+}
+
+static int plan_stats_impl(rip_handle* h, const float* z_dev, const float* y_dev, int B, int M, float* q_dev,
+                           float* stats_dev, rip_stream_t stream) {
+  int rc = check_models(h, 0, h ? h->K : 1);
+  if (rc != RIP_OK) return rc;
+  REQUIRE(z_dev != nullptr, "z_dev is NULL");
+  REQUIRE(y_dev != nullptr, "y_dev is NULL");
+  REQUIRE(B >= 1 && M >= 1 && (long long)B * M <= 0x7fffffffLL, "bad shape B=%d M=%d", B, M);
+  REQUIRE(q_dev != nullptr || stats_dev != nullptr, "q_dev and stats_dev are both NULL");
+  ENTER(h, stream);
+  HIP_TRY(launch_ensemble_stats(h->flow_w, h->K, z_dev, y_dev, B, M, q_dev, stats_dev, (hipStream_t)stream));
+  return RIP_OK;
+}
+
+int rip_plan_stats(rip_handle* h, const float* z_dev, const float* y_dev, int B, int M, float* q_dev, float* stats_dev,
+                   rip_stream_t stream) {
+  return plan_stats_impl(h, z_dev, y_dev, B, M, q_dev, stats_dev, stream);
+}
+
+int rip_act_stats(rip_handle* h, const float* lidar_dev, int channels_last, int H, int W, const float* vec_dev,
+                  const float* goal_dev, const float* x0_dev, int B, int N, int G, int algorithm, int num_steps, float lr,
+                  float epsilon, int enc_dtype, float* plan_dev, float* loss_best_dev, double* plan_interp_dev,
+                  float* q_dev, float* stats_dev, rip_stream_t stream) {
+  if (q_dev == nullptr && stats_dev == nullptr)
+    return rip_act(h, lidar_dev, channels_last, H, W, vec_dev, goal_dev, x0_dev, B, N, G, algorithm, num_steps, lr, epsilon,
+                   enc_dtype, plan_dev, loss_best_dev, plan_interp_dev, stream);
+  REQUIRE(h != nullptr, "handle is NULL");
+  REQUIRE(plan_dev != nullptr || plan_interp_dev != nullptr, "plan_dev and plan_interp_dev are both NULL");
+  int rc = rip_encode_raw(h, lidar_dev, channels_last, H, W, vec_dev, B, 0, h->K, enc_dtype, h->z, stream);  // B <= max_batch
+  if (rc != RIP_OK) return rc;
+  float* plan = plan_dev != nullptr ? plan_dev : h->stat_plan;
+  rc = search_impl(h, h->z, goal_dev, x0_dev, B, N, G, algorithm, num_steps, lr, epsilon, plan, nullptr, loss_best_dev,
+                   nullptr, nullptr, nullptr, nullptr, plan_interp_dev, stream);
+  if (rc != RIP_OK) return rc;
+  return plan_stats_impl(h, h->z, plan, B, 1, q_dev, stats_dev, stream);
 }
 
 static int fill_mp(rip_handle* h, MpArgs& a, int k_fwd, int k_begin, int k_count, int first_is_fwd, const float* z_fwd,

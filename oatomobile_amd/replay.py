@@ -602,14 +602,17 @@ class DeviceCache:
 
 
 def replay_cache(agent, cache: "PackedCache", batch_size: int, interpolate: bool = False, begin: int = 0,
-                 end: Optional[int] = None, streams: int = 1) -> np.ndarray:
+                 end: Optional[int] = None, streams: int = 1, stats: bool = False):
   """`replay()` from a packed cache: plans of observations [begin, end) -> [n,4,2] float32, or with `interpolate` the
   [n,30,3] float64 plans `agent(observation)` returns.  Per batch: one memcpy out of the page cache into pinned staging
   (80 KB per observation), H2D on a copy stream under the previous batch's kernels, `RIPAgent.plan_batch_coded`, D2H of
   the plans into pinned memory.  Ranks of a multi-GPU job take `distributed.shard_range(len(cache), rank, world)`.
   `streams=2` (round 6): even batches run on `agent`, odd batches on `agent.twin()` — a second handle — each on a stream
   of its own, so that one batch's encoder launches (whose grids leave CUs idle at their tails) run beside the other
-  batch's search; the plans are the same bits (same kernels, same inputs, rows written to disjoint slices of the result)."""
+  batch's search; the plans are the same bits (same kernels, same inputs, rows written to disjoint slices of the result).
+  `stats=True` returns `(plans, stats [n,4] float32, q [n,K] float32)`: per observation the ensemble disagreement of its
+  plan (`RIPAgent.plan_batch_coded(return_stats=True)`: mean, population variance, min, max of the K members' log q_k,
+  and the K values), rows in the same disjoint slices."""
   if streams not in (1, 2):
     raise ValueError("replay_cache: streams must be 1 or 2")
   dev = agent._device
@@ -617,8 +620,11 @@ def replay_cache(agent, cache: "PackedCache", batch_size: int, interpolate: bool
   n = max(0, end - begin)
   shape, ndt, tdt = ((n, 30, 3), np.float64, torch.float64) if interpolate else ((n, 4, 2), np.float32, torch.float32)
   out = torch.empty(shape, dtype=tdt, pin_memory=True)
+  K = len(agent._models)
+  out_s = torch.empty((n, 4), dtype=torch.float32, pin_memory=True) if stats else None
+  out_q = torch.empty((n, K), dtype=torch.float32, pin_memory=True) if stats else None
   if n == 0:
-    return out.numpy()
+    return (out.numpy(), out_s.numpy(), out_q.numpy()) if stats else out.numpy()
   lut = torch.from_numpy(cache.lut).to(dev)
   copy = torch.cuda.Stream(device=dev)
   main = torch.cuda.current_stream(dev)
@@ -657,9 +663,54 @@ def replay_cache(agent, cache: "PackedCache", batch_size: int, interpolate: bool
       filled[j].record(copy)
     with torch.cuda.stream(lanes[j]):  # (one stream: the current stream itself)
       lanes[j].wait_event(ready[j])
-      plan = agents[j].plan_batch_coded(dslots[j][0][:m], lut, dslots[j][1][:m], dslots[j][2][:m], interpolate=interpolate)
+      if stats:
+        plan, ps = agents[j].plan_batch_coded(dslots[j][0][:m], lut, dslots[j][1][:m], dslots[j][2][:m],
+                                              interpolate=interpolate, return_stats=True)
+        out_s[i0:i0 + m].copy_(torch.stack((ps.mean, ps.variance, ps.min, ps.max), dim=1), non_blocking=True)
+        out_q[i0:i0 + m].copy_(ps.q.t(), non_blocking=True)
+      else:
+        plan = agents[j].plan_batch_coded(dslots[j][0][:m], lut, dslots[j][1][:m], dslots[j][2][:m], interpolate=interpolate)
       out[i0:i0 + m].copy_(plan, non_blocking=True)
       freed[j].record(lanes[j])
     i0 += m
   torch.cuda.synchronize(dev)
-  return out.numpy()
+  return (out.numpy(), out_s.numpy(), out_q.numpy()) if stats else out.numpy()
+
+
+def score_cache(agent, data: "DeviceCache", batch_size: int) -> dict:
+  """The per-member expert log-likelihood and its ensemble statistics over a whole device-resident cache, one pass:
+  for every row the trajectory is the expert's future as the model sees it (`data.batch(rows, 4)["player_future"]` =
+  `future[:, 0::L // 4]`), the batch's already transformed `visual_features` go through `rip_encode` for the K members
+  of `agent` (a `RIPAgent` with `max_batch >= batch_size`), then one `rip_plan_stats` launch per batch.
+  -> dict(q [n,K] float32 = log q_k(expert | x), stats [n,4] float32 = its mean, population variance, min, max over k)."""
+  from oatomobile_amd import _lib, arch
+  dev = agent._device
+  if data.device != dev:
+    raise RuntimeError("score_cache: the cache is on %s, the agent on %s" % (data.device, dev))
+  if data.channels != agent._in_channels:
+    raise ValueError("score_cache: the cache has %d BEV channels, the agent expects %d" % (data.channels, agent._in_channels))
+  batch_size = int(batch_size)
+  if batch_size < 1 or batch_size > agent._max_batch:
+    raise ValueError("score_cache: batch_size %d outside [1, max_batch=%d]" % (batch_size, agent._max_batch))
+  n, K = len(data), len(agent._models)
+  if agent._sync_weights():
+    agent._online = {}
+  q = torch.empty((n, K), device=dev, dtype=torch.float32)
+  stats = torch.empty((n, _lib.STAT_SLOTS), device=dev, dtype=torch.float32)
+  lib, h = _lib.load(), agent._handle
+  z = torch.empty((K, batch_size, 64), device=dev, dtype=torch.float32)
+  qb = torch.empty((K, batch_size), device=dev, dtype=torch.float32)
+  agent._eager_pending = True
+  for i0 in range(0, n, batch_size):
+    m = min(batch_size, n - i0)
+    batch = data.batch(torch.arange(i0, i0 + m, device=dev), arch.T)
+    vec = torch.cat((batch["velocity"], batch["is_at_traffic_light"], batch["traffic_light_state"]), dim=1)  # [m,5]
+    zb, qv = z.view(-1)[:K * m * 64].view(K, m, 64), qb.view(-1)[:K * m].view(K, m)
+    st = h.stream()
+    _lib.check(lib.rip_encode(h.raw, _lib.ptr(batch["visual_features"]), _lib.ptr(vec), m, 0, K, agent._enc_dtype,
+                              _lib.ptr(zb), None, st))
+    _lib.check(lib.rip_plan_stats(h.raw, _lib.ptr(zb), _lib.ptr(batch["player_future"]), m, 1, _lib.ptr(qv),
+                                  _lib.ptr(stats[i0:i0 + m]), st))
+    q[i0:i0 + m].copy_(qv.t())
+  torch.cuda.synchronize(dev)
+  return dict(q=q.cpu().numpy(), stats=stats.cpu().numpy())

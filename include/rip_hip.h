@@ -28,7 +28,7 @@
  *     makes that device current for the duration of the call and restores the
  *     caller's current device before returning.  The stateless entry points
  *     (rip_transform, rip_goal_likelihood, rip_goal_likelihood_vjp,
- *     rip_lidar_bev, rip_cil_decode, rip_gather_batch_u8) launch
+ *     rip_lidar_bev, rip_cil_decode, rip_gather_batch_u8, rip_sample_normal) launch
  *     on the caller's current device, which must own the pointers.
  *   - a handle's scratch is shared by its calls, so a handle is single-stream
  *     and not thread-safe: when consecutive calls on one handle name different
@@ -305,6 +305,40 @@ int rip_act_stats(rip_handle* h, const float* lidar_dev, int channels_last, int 
                   const float* goal_dev, const float* x0_dev, int B, int N, int G, int algorithm, int num_steps, float lr,
                   float epsilon, int enc_dtype, float* plan_dev, float* loss_best_dev, double* plan_interp_dev,
                   float* q_dev, float* stats_dev, rip_stream_t stream);
+
+/* Sample-and-rank ensemble prediction: the open-loop use of a deep ensemble of imitative models (Filos et al. 2020,
+ * evaluated there as minADE_k / minFDE_k of the top-k set).  K members, B observations, S samples per member: M = K S
+ * candidates per observation, candidate m = j S + s drawn from member j = m / S.
+ *
+ * The generator is counter-based, so a sample depends on (seed, sample id) alone and never on the launch shape:
+ * Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with key
+ * (seed & 0xffffffff, seed >> 32) and counter (g & 0xffffffff, g >> 32, c, 0) for the 64-bit sample id g and the call
+ * c in {0, 1}; call c fills x[4c .. 4c+3] of the latent x[4][2] by Box-Muller on the word pairs (w0, w1) and (w2, w3) in
+ * fp32 with the accurate logf / sincosf: u = ((wa >> 8) + 1) 2^-24, v = (wb >> 8) 2^-24, r = sqrt(-2 ln u), outputs
+ * r cos(2 pi v), r sin(2 pi v); |x| <= 5.77, never infinite.
+ *
+ * rip_sample_normal: the generator alone, stateless: out_dev [n,8] = the latents of sample ids first_id .. first_id+n-1. */
+int rip_sample_normal(uint64_t seed, uint64_t first_id, int64_t n, float* out_dev, rip_stream_t stream);
+
+/* rip_predict, three launches on z_dev [K,B,64] (rip_encode / rip_encode_raw of the K members):
+ *   1. y_all_dev [B,M,4,2]: candidate j S + s = AutoregressiveFlow._forward of member j (sequence.py:96-151) on the
+ *      latent noise_dev [B,K,S,4,2], or with noise_dev NULL on the generator's sample g = ((row0 + b) K + j) S + s — row0
+ *      is the index of this call's first observation in the caller's data set, so that a data set gives the same
+ *      samples whatever the batch size;
+ *   2. q_dev [K,B,M] and stats_dev [B,M,RIP_STAT_SLOTS]: rip_plan_stats on y_all_dev, the same launch and the same
+ *      bits (a member's own samples are scored by its inverse pass like everyone else's);
+ *   3. loss [B,M] by `algorithm` as rip_aggregate_scores has it (WCM min_k(-q), BCM max_k(-q), MA mean_k(-q)), minus
+ *      rip_goal_likelihood of the last waypoint under goal_dev [B,G,2] when that is not NULL (G <= 64), written to
+ *      loss_all_dev (NULL to skip); then the top_k lowest losses per observation in ascending order, ties to the lower
+ *      candidate index, NaN last: y_top_dev [B,top_k,4,2], loss_top_dev [B,top_k], index_top_dev [B,top_k] (member =
+ *      index / S), and against target_dev [B,4,2] the displacement errors ade_dev / fde_dev [B,top_k] (mean over the 4
+ *      steps, and step 3, of the Euclidean distance; either may be NULL, both must be without a target).
+ * The caller owns every buffer; nothing is kept in the handle.  RIP_EINVAL (nothing is launched) unless 1 <= S,
+ * M <= 4096, 1 <= top_k <= min(M, 64), B >= 1, B M < 2^31, row0 >= 0 and the required pointers are set. */
+int rip_predict(rip_handle* h, const float* z_dev, const float* goal_dev, int G, float epsilon, const float* target_dev,
+                const float* noise_dev, uint64_t seed, int64_t row0, int B, int S, int top_k, int algorithm,
+                float* y_all_dev, float* q_dev, float* stats_dev, float* loss_all_dev, float* y_top_dev,
+                float* loss_top_dev, int32_t* index_top_dev, float* ade_dev, float* fde_dev, rip_stream_t stream);
 
 /* N3 — the DIM training step, oatomobile/baselines/torch/dim/train.py:175-213:
  *   z = model._params(...) in TRAIN mode (MobileNetV2 BatchNorm on batch statistics with the running-stat update,

@@ -7,7 +7,7 @@ __graft_entry__ as g; g.build()"` (hipcc, gfx950) first.
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librip_hip.so")
@@ -65,6 +65,11 @@ SIGNATURES = [
     ("rip_act_stats", c_int, [
         c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
         c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p
+    ]),
+    ("rip_sample_normal", c_int, [c_uint64, c_uint64, c_int64, c_void_p, c_void_p]),
+    ("rip_predict", c_int, [
+        c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_uint64, c_int64, c_int, c_int, c_int, c_int,
+        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p
     ]),
     ("rip_interpolate_plans", c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     ("rip_search_plan", c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),

@@ -17,6 +17,7 @@ import torch
 
 from oatomobile_amd import _lib
 from oatomobile_amd import arch
+from oatomobile_amd import prediction
 from oatomobile_amd.model import ImitativeModel
 
 SIMULATOR_FPS = 20  # base.py:31
@@ -267,11 +268,12 @@ class RIPAgent(SetPointAgent):
     return self._x0_cache[batch]
 
   def _check_batch(self, lidar: torch.Tensor, vec: torch.Tensor, goal: Optional[torch.Tensor], y: Optional[torch.Tensor] = None,
-                   what: str = "plan_batch") -> None:
+                   what: str = "plan_batch", pair_only: bool = False) -> None:
     """The C ABI takes raw pointers: dtype, device and shape are enforced here (ValueError / RuntimeError).  `goal`
-    [B,G,2] (plan_batch) or `y` [B,4,2] / [B,M,4,2] (score_trajectories) is the third input."""
+    [B,G,2] (plan_batch) or `y` [B,4,2] / [B,M,4,2] (score_trajectories) is the third input; `pair_only` (predict_batch)
+    checks lidar and vec alone."""
     third = ("goal", goal) if y is None else ("y", y)
-    for name, t in (("lidar", lidar), ("vec", vec), third):
+    for name, t in (("lidar", lidar), ("vec", vec)) + (() if pair_only else (third,)):
       if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self._device:
         raise RuntimeError("%s: `%s` must be a tensor on %s (got %s)" %
                            (what, name, self._device, getattr(t, "device", type(t))))
@@ -283,6 +285,8 @@ class RIPAgent(SetPointAgent):
       raise ValueError("%s: lidar %s: batch must be in [1, max_batch=%d], H, W >= 1" %
                        (what, tuple(lidar.shape), self._max_batch))
     _lib.expect_shape(vec, (b, 5), "vec")
+    if pair_only:  # predict_batch: its optional goal / target / noise are checked by _check_predict
+      return
     if y is not None:
       _lib.expect_shape(y, (b, arch.T, 2) if y.dim() == 3 else (b, None, arch.T, 2), "y")
       if y.shape[1] < 1:
@@ -395,6 +399,110 @@ class RIPAgent(SetPointAgent):
       _lib.check(lib.rip_plan_stats(self._handle.raw, _lib.ptr(z), _lib.ptr(target), b, 1, _lib.ptr(q), _lib.ptr(stats), st))
       return out, _plan_stats(q, stats)
     return out
+
+  def _check_predict(self, what: str, b: int, num_samples, top_k, goal, target, noise, row0, seed):
+    """The argument checks of `predict_batch*` behind the input checks (ValueError / RuntimeError before any launch)
+    -> (S, top_k) as ints."""
+    K = len(self._models)
+    if isinstance(num_samples, bool) or not isinstance(num_samples, (int, np.integer)) or num_samples < 1:
+      raise ValueError("%s: num_samples must be an integer >= 1, got %r" % (what, num_samples))
+    S = int(num_samples)
+    M = K * S
+    if M > prediction.MAX_CANDIDATES:
+      raise ValueError("%s: K x num_samples = %d x %d = %d candidates per observation, at most %d" %
+                       (what, K, S, M, prediction.MAX_CANDIDATES))
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= min(M, prediction.MAX_TOP_K):
+      raise ValueError("%s: top_k must be an integer in [1, min(M=%d, %d)], got %r" % (what, M, prediction.MAX_TOP_K, top_k))
+    if int(row0) < 0 or not 0 <= int(seed) < 2**64:
+      raise ValueError("%s: row0 >= 0 and 0 <= seed < 2**64, got row0=%r seed=%r" % (what, row0, seed))
+    for name, t, shape in (("goal", goal, (b, None, 2)), ("target", target, (b, arch.T, 2)),
+                           ("noise", noise, (b, K, S, arch.T, 2))):
+      if t is None:
+        continue
+      if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self._device:
+        raise RuntimeError("%s: `%s` must be a tensor on %s (got %s)" % (what, name, self._device, getattr(t, "device", type(t))))
+      if t.dtype != torch.float32:
+        raise ValueError("%s: `%s` must be float32, got %s" % (what, name, t.dtype))
+      _lib.expect_shape(t, shape, name)
+    if goal is not None and not 1 <= goal.shape[1] <= 64:
+      raise ValueError("%s: goal needs 1 to 64 waypoints, got %d" % (what, goal.shape[1]))
+    return S, int(top_k)
+
+  def _predict(self, z, b: int, S: int, top_k: int, goal, target, noise, seed, row0, return_candidates: bool):
+    """`rip_predict` on z [K,b,64] into fresh outputs -> `Prediction` (and the candidate set)."""
+    K, dev = len(self._models), self._device
+    M = K * S
+    f32 = dict(device=dev, dtype=torch.float32)
+    y_all, q = torch.empty((b, M, arch.T, 2), **f32), torch.empty((K, b, M), **f32)
+    stats = torch.empty((b, M, _lib.STAT_SLOTS), **f32)
+    loss_all = torch.empty((b, M), **f32) if return_candidates else None
+    y_top, loss_top = torch.empty((b, top_k, arch.T, 2), **f32), torch.empty((b, top_k), **f32)
+    index = torch.empty((b, top_k), device=dev, dtype=torch.int32)
+    ade = torch.empty((b, top_k), **f32) if target is not None else None
+    fde = torch.empty((b, top_k), **f32) if target is not None else None
+    goal = None if goal is None else goal.contiguous()
+    target = None if target is None else target.contiguous()
+    noise = None if noise is None else noise.contiguous()
+    _lib.check(_lib.load().rip_predict(
+        self._handle.raw, _lib.ptr(z), _lib.ptr(goal), 0 if goal is None else goal.shape[1], self._epsilon, _lib.ptr(target),
+        _lib.ptr(noise), int(seed), int(row0), b, S, top_k, _lib.ALGORITHMS[self._algorithm], _lib.ptr(y_all), _lib.ptr(q),
+        _lib.ptr(stats), _lib.ptr(loss_all), _lib.ptr(y_top), _lib.ptr(loss_top), _lib.ptr(index, torch.int32), _lib.ptr(ade),
+        _lib.ptr(fde), self._handle.stream()))
+    pred = prediction.Prediction(y_top, loss_top, index, torch.div(index, S, rounding_mode="floor"), ade, fde)
+    return (pred, y_all, q, loss_all) if return_candidates else pred
+
+  def predict_batch(self, lidar: torch.Tensor, vec: torch.Tensor, *, num_samples: int, top_k: int = 1,
+                    goal: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, seed: int = 0,
+                    row0: int = 0, noise: Optional[torch.Tensor] = None, return_candidates: bool = False):
+    """Open-loop ensemble prediction by sample-and-rank: lidar [B,H,W,C], vec [B,5] as `plan_batch`.  Every member j
+    draws `num_samples` = S trajectories from its flow, all M = K S candidates (m = j S + s) are scored under all K
+    members and aggregated with the agent's `algorithm` (minus the goal likelihood when `goal` [B,G,2] is given, with
+    the agent's `epsilon`), and the `top_k` (<= min(M, 64)) lowest losses come back best-first as a `Prediction` of
+    device tensors; with `target` [B,4,2] (the expert's future) it carries their displacement errors.  One
+    `rip_encode_raw` for the K members, then one `rip_predict`.
+    The latents come from the device's counter-based generator: sample ((row0 + b) K + j) S + s of `seed`
+    (`prediction.philox_normal` on the host), so a data set walked in batches — `row0` = the index of the batch's first
+    observation — draws the same samples whatever the batch size.  `noise` [B,K,S,4,2] replaces them.
+    `return_candidates=True` appends `(y_all [B,M,4,2], q [K,B,M], loss_all [B,M])`: every candidate, the log q_k
+    `rip_plan_stats` gives for it, and its loss."""
+    self._check_batch(lidar, vec, None, what="predict_batch", pair_only=True)
+    S, top_k = self._check_predict("predict_batch", lidar.shape[0], num_samples, top_k, goal, target, noise, row0, seed)
+    if self._sync_weights():
+      self._online = {}
+    lidar, vec = lidar.contiguous(), vec.contiguous()
+    b, K = lidar.shape[0], len(self._models)
+    z = torch.empty(K, b, 64, device=self._device, dtype=torch.float32)
+    self._eager_pending = True
+    _lib.check(_lib.load().rip_encode_raw(self._handle.raw, _lib.ptr(lidar), 1, lidar.shape[1], lidar.shape[2], _lib.ptr(vec),
+                                          b, 0, K, self._enc_dtype, _lib.ptr(z), self._handle.stream()))
+    return self._predict(z, b, S, top_k, goal, target, noise, seed, row0, return_candidates)
+
+  def predict_batch_coded(self, codes: torch.Tensor, lut: torch.Tensor, vec: torch.Tensor, *, num_samples: int,
+                          top_k: int = 1, goal: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
+                          seed: int = 0, row0: int = 0, noise: Optional[torch.Tensor] = None,
+                          return_candidates: bool = False):
+    """`predict_batch` on a CODED BEV (the replay cache): codes [B,H,W,C] uint8 indices into lut [256] float32, as
+    `plan_batch_coded` takes them (`rip_encode_raw_u8`, then `rip_predict`): the bits of `predict_batch` on the float32
+    BEV."""
+    dev = self._device
+    if not (isinstance(codes, torch.Tensor) and codes.is_cuda and codes.device == dev and codes.dtype == torch.uint8):
+      raise ValueError("predict_batch_coded: `codes` must be a uint8 tensor on %s" % (dev,))
+    _lib.expect_shape(codes, (None, None, None, self._in_channels), "codes")
+    b = codes.shape[0]
+    if b < 1 or b > self._max_batch:
+      raise ValueError("predict_batch_coded: batch %d outside [1, max_batch=%d]" % (b, self._max_batch))
+    _lib.expect_shape(lut, (256,), "lut")
+    _lib.expect_shape(vec, (b, 5), "vec")
+    S, top_k = self._check_predict("predict_batch_coded", b, num_samples, top_k, goal, target, noise, row0, seed)
+    if self._sync_weights():
+      self._online = {}
+    codes, vec, K = codes.contiguous(), vec.contiguous(), len(self._models)
+    z = torch.empty(K, b, 64, device=dev, dtype=torch.float32)
+    self._eager_pending = True
+    _lib.check(_lib.load().rip_encode_raw_u8(self._handle.raw, _lib.ptr(codes, torch.uint8), _lib.ptr(lut), codes.shape[1],
+                                             codes.shape[2], _lib.ptr(vec), b, 0, K, self._enc_dtype, _lib.ptr(z),
+                                             self._handle.stream()))
+    return self._predict(z, b, S, top_k, goal, target, noise, seed, row0, return_candidates)
 
   def _launch_act(self, lidar, vec, goal, plan, loss, plan_interp=None, q=None, stats=None) -> None:
     b = lidar.shape[0]

@@ -112,6 +112,20 @@ hipError_t launch_score(const float* flow_w, int k0, int K, const float* z, cons
 // min, max) over the members, reduced in model order without atomics.  Either output may be nullptr.  K <= MAX_MODELS.
 hipError_t launch_ensemble_stats(const float* flow_w, int K, const float* z, const float* y, int B, int M, float* q,
                                  float* stats, hipStream_t s);
+// Sample-and-rank prediction (rip_predict), three launches.  Generator: Philox4x32-10 keyed by the seed, counter =
+// (sample id, call c in {0, 1}), Box-Muller in fp32: out [n][8] = the latents of sample ids first_id .. first_id + n - 1.
+hipError_t launch_sample_normal(unsigned long long seed, unsigned long long first_id, long long n, float* out,
+                                hipStream_t s);
+// y_all [B][K S][8]: candidate j S + s of observation b = F_j(x; z[j][b]) with x = noise [B][K][S][8], or when that is
+// nullptr the generator's sample ((row0 + b) K + j) S + s.
+hipError_t launch_sample_forward(const float* flow_w, int K, const float* z, const float* noise, unsigned long long seed,
+                                 unsigned long long row0, int B, int S, float* y_all, hipStream_t s);
+// stats [B][M][4] (launch_ensemble_stats) -> loss [B][M] by `algorithm` (minus the goal likelihood when goal != nullptr)
+// and the top_k <= 64 lowest per observation, ascending, ties to the lower index, NaN last: y_top [B][top_k][8],
+// loss_top / index_top [B][top_k], and against target [B][8] ade / fde [B][top_k].  M <= 4096.
+hipError_t launch_rank(const float* stats, const float* y_all, const float* goal, const float* target, int B, int M, int G,
+                       float eps, int algorithm, int top_k, float* loss_all, float* y_top, float* loss_top,
+                       int32_t* index_top, float* ade, float* fde, hipStream_t s);
 hipError_t launch_search(const SearchArgs& a, hipStream_t s);
 hipError_t launch_select_best(const float* plans, const float* loss_best, int B, int N, float* plan, int32_t* best,
                               double* interp /*[B][30][3] or nullptr*/, hipStream_t s);

@@ -647,6 +647,194 @@ __global__ __launch_bounds__(256) void ensemble_stats_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------
+// sample-and-rank prediction: a counter-based generator, the sampling pass and the ranking / metric kernel
+// ------------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32 x 32 -> 64 multiplies, the key bumped by the Weyl constants
+// between rounds.  A sample is a function of (key, counter) alone, never of the launch shape.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&w)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  w[0] = c0;
+  w[1] = c1;
+  w[2] = c2;
+  w[3] = c3;
+}
+
+// Box-Muller on one word pair in fp32 with the accurate logf / sincosf: u in (0, 1] and v in [0, 1) on a 2^-24 grid, so
+// r <= sqrt(48 ln 2) = 5.77 and nothing is infinite.
+__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& a, float& b) {
+  const float u = (float)((wa >> 8) + 1u) * 5.9604644775390625e-08f;
+  const float v = (float)(wb >> 8) * 5.9604644775390625e-08f;
+  const float r = sqrtf(-2.0f * logf(u));
+  float sn, cs;
+  sincosf(6.283185307179586f * v, &sn, &cs);
+  a = r * cs;
+  b = r * sn;
+}
+
+// Call c in {0, 1} of sample id g: the normals x[4c .. 4c+3] of the latent x[4][2] of that sample.
+__device__ __forceinline__ void sample_normal4(unsigned long long seed, unsigned long long g, uint32_t c, float (&x)[4]) {
+  uint32_t w[4];
+  philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), c, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+  box_muller(w[0], w[1], x[0], x[1]);
+  box_muller(w[2], w[3], x[2], x[3]);
+}
+
+__global__ void sample_normal_kernel(unsigned long long seed, unsigned long long first_id, long long n,
+                                     float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // one generator call per thread
+  if (i >= 2 * n) return;
+  float x[4];
+  sample_normal4(seed, first_id + (unsigned long long)(i >> 1), (uint32_t)(i & 1), x);
+  *reinterpret_cast<float4*>(out + (size_t)i * 4) = make_float4(x[0], x[1], x[2], x[3]);
+}
+
+// y_all[b][j * S + s] = F_j(x; z[j][b]) for the S latents of (observation b, member j): flow_rows_kernel's structure with
+// blockIdx.y = j (member j's weights are loaded once per wave).  A wave walks a contiguous span of (b, s) rows, so that
+// the prefix of (b, j) is reused over its samples.  x is the generator's sample ((row0 + b) K + j) S + s, or the caller's
+// noise[b][j][s][8].
+__global__ __launch_bounds__(256) void sample_forward_kernel(const float* __restrict__ flow_w,
+                                                              const float* __restrict__ z,
+                                                              const float* __restrict__ noise, unsigned long long seed,
+                                                              unsigned long long row0, int B, int K, int S, int span,
+                                                              float* __restrict__ y_all) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* w1 = smem;
+  float* io = smem + W1_LDS;  // per wave: 8 in + 8 out
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  const int j = blockIdx.y;
+  const float* blob = flow_w + (size_t)j * FW_SIZE;
+  stage_w1(w1, blob, tid, blockDim.x);
+  FlowRegs W;
+  load_flow_regs(W, blob, lane);
+  __syncthreads();
+  const float* w1row = w1 + (lane & 31) * W1_STRIDE;
+  float* my_in = io + wave * 16;
+  float* my_out = my_in + 8;
+  const long long rows = (long long)B * S;
+  const long long r0 = ((long long)blockIdx.x * nw + wave) * span;
+  const long long r1 = r0 + span < rows ? r0 + span : rows;
+  Prefix pre;
+  int pre_b = -1;
+#pragma unroll 1
+  for (long long row = r0; row < r1; ++row) {
+    const int b = (int)(row / S), s = (int)(row - (long long)b * S);
+    if (noise != nullptr) {
+      if (lane < 8) my_in[lane] = noise[((((size_t)b * K + j) * S) + s) * 8 + lane];
+    } else if (lane < 2) {
+      float x[4];
+      sample_normal4(seed, ((row0 + (unsigned long long)b) * K + j) * S + s, (uint32_t)lane, x);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) my_in[4 * lane + i] = x[i];
+    }
+    if (b != pre_b) {
+      pre = chain_prefix(W, w1row, z[((size_t)j * B + b) * 64 + lane]);
+      pre_b = b;
+    }
+    __builtin_amdgcn_wave_barrier();
+    chain_forward<false>(MODE_FWD, W, w1row, pre, my_in, my_out, nullptr, lane);
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 8) y_all[(((size_t)b * K + j) * S + s) * 8 + lane] = my_out[lane];
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// A float as an unsigned key whose order is the order np.argsort gives: ascending, -0 == +0, every NaN last.
+__device__ __forceinline__ uint32_t rank_key(float l) {
+  if (l != l) return 0xFFFFFFFFu;
+  if (l == 0.f) l = 0.f;
+  const uint32_t u = __float_as_uint(l);
+  return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+
+// One workgroup per observation: loss[m] of the M = K S candidates from the ensemble statistics (aggregate_scores_kernel's
+// convention: WCM min_k(-q) = -max, BCM max_k(-q) = -min, MA -mean; minus the goal likelihood of the last waypoint when
+// a goal is given), then the top_k lowest in ascending order of (loss, m) — ties to the lower m, NaN last — by top_k
+// rounds of a workgroup arg-min over the keys above the last one chosen (top_k <= 64; M may exceed the workgroup: every
+// pass strides).  Writes the chosen trajectories, losses and indices, and against a target the average / final
+// displacement errors (accumulated in double, so that the result is the rounded float of the exact value).
+constexpr int RANK_THREADS = 256;
+constexpr int RANK_MAX_TOP = 64;
+__global__ __launch_bounds__(RANK_THREADS) void rank_kernel(const float* __restrict__ stats, const float* __restrict__ y_all,
+                                                            const float* __restrict__ goal,
+                                                            const float* __restrict__ target, int M, int G, float eps,
+                                                            int algorithm, int top_k, float* __restrict__ loss_all,
+                                                            float* __restrict__ y_top, float* __restrict__ loss_top,
+                                                            int32_t* __restrict__ index_top, float* __restrict__ ade,
+                                                            float* __restrict__ fde) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* loss = smem;                                         // [M]
+  uint32_t* key = reinterpret_cast<uint32_t*>(smem + M);      // [M]
+  __shared__ unsigned long long wmin[2][RANK_THREADS / 64];
+  __shared__ int sel[RANK_MAX_TOP];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* st = stats + (size_t)b * M * 4;
+  const float* yb = y_all + (size_t)b * M * 8;
+  for (int m = tid; m < M; m += RANK_THREADS) {
+    const float4 v = *reinterpret_cast<const float4*>(st + (size_t)m * 4);  // mean, variance, min, max
+    float l = algorithm == ALGO_WCM ? -v.w : (algorithm == ALGO_BCM ? -v.z : -v.x);
+    if (goal != nullptr) l -= goal_ll(goal + (size_t)b * G * 2, G, eps, yb[m * 8 + 6], yb[m * 8 + 7], nullptr, nullptr);
+    loss[m] = l;
+    key[m] = rank_key(l);
+    if (loss_all != nullptr) loss_all[(size_t)b * M + m] = l;
+  }
+  __syncthreads();
+  unsigned long long floor_key = 0;  // the smallest key still eligible
+#pragma unroll 1
+  for (int i = 0; i < top_k; ++i) {
+    unsigned long long best = ~0ull;
+    for (int m = tid; m < M; m += RANK_THREADS) {
+      const unsigned long long k64 = ((unsigned long long)key[m] << 32) | (unsigned)m;
+      if (k64 >= floor_key && k64 < best) best = k64;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const uint32_t ohi = __shfl_xor((uint32_t)(best >> 32), d, 64), olo = __shfl_xor((uint32_t)best, d, 64);
+      const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
+      best = o < best ? o : best;
+    }
+    if (lane == 0) wmin[i & 1][wave] = best;
+    __syncthreads();
+    best = wmin[i & 1][0];
+#pragma unroll
+    for (int w = 1; w < RANK_THREADS / 64; ++w) best = wmin[i & 1][w] < best ? wmin[i & 1][w] : best;
+    if (tid == 0) sel[i] = (int)(uint32_t)best;
+    floor_key = best + 1;
+  }
+  __syncthreads();
+  for (int t = tid; t < top_k * 8; t += RANK_THREADS)
+    y_top[((size_t)b * top_k) * 8 + t] = yb[(size_t)sel[t >> 3] * 8 + (t & 7)];
+  if (tid < top_k) {
+    const int m = sel[tid];
+    const size_t o = (size_t)b * top_k + tid;
+    loss_top[o] = loss[m];
+    index_top[o] = m;
+    if (target != nullptr) {
+      const float* tg = target + (size_t)b * 8;
+      double sum = 0.0, d = 0.0;
+      for (int t = 0; t < T; ++t) {
+        const double d0 = (double)yb[(size_t)m * 8 + 2 * t] - (double)tg[2 * t];
+        const double d1 = (double)yb[(size_t)m * 8 + 2 * t + 1] - (double)tg[2 * t + 1];
+        d = sqrt(d0 * d0 + d1 * d1);
+        sum += d;
+      }
+      if (ade != nullptr) ade[o] = (float)(sum / T);
+      if (fde != nullptr) fde[o] = (float)d;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // fused plan search: one workgroup per (observation b, candidate n); NW waves share the K models
 // ------------------------------------------------------------------------------------------
 struct SearchShared {
@@ -1800,6 +1988,37 @@ hipError_t launch_ensemble_stats(const float* flow_w, int K, const float* z, con
   const size_t lds = (size_t)(nw * (W1_LDS + 8) + per * MAX_MODELS) * sizeof(float);
   hipLaunchKernelGGL(ensemble_stats_kernel, dim3((rows + per - 1) / per), dim3(nw * 64), lds, s, flow_w, K, z, y, B, M,
                      per, q, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_sample_normal(unsigned long long seed, unsigned long long first_id, long long n, float* out,
+                                hipStream_t s) {
+  const long long calls = 2 * n;
+  hipLaunchKernelGGL(sample_normal_kernel, dim3((unsigned)((calls + 255) / 256)), dim3(256), 0, s, seed, first_id, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_sample_forward(const float* flow_w, int K, const float* z, const float* noise, unsigned long long seed,
+                                 unsigned long long row0, int B, int S, float* y_all, hipStream_t s) {
+  // rows per wave: what spreads the B S rows of a member over 2048 waves, and at least min(S, 4) so that a prefix serves
+  // several samples
+  const long long rows = (long long)B * S;
+  long long span = (rows + 2047) / 2048;
+  const long long share = S < 4 ? S : 4;
+  span = span < share ? share : span;
+  const long long waves = (rows + span - 1) / span;
+  const size_t lds = (W1_LDS + 4 * 16) * sizeof(float);
+  hipLaunchKernelGGL(sample_forward_kernel, dim3((unsigned)((waves + 3) / 4), K), dim3(256), lds, s, flow_w, z, noise, seed,
+                     row0, B, K, S, (int)span, y_all);
+  return hipGetLastError();
+}
+
+hipError_t launch_rank(const float* stats, const float* y_all, const float* goal, const float* target, int B, int M, int G,
+                       float eps, int algorithm, int top_k, float* loss_all, float* y_top, float* loss_top,
+                       int32_t* index_top, float* ade, float* fde, hipStream_t s) {
+  const size_t lds = (size_t)M * 2 * sizeof(float);
+  hipLaunchKernelGGL(rank_kernel, dim3(B), dim3(RANK_THREADS), lds, s, stats, y_all, goal, target, M, G, eps, algorithm,
+                     top_k, loss_all, y_top, loss_top, index_top, ade, fde);
   return hipGetLastError();
 }
 

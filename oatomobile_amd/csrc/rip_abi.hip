@@ -993,6 +993,46 @@ int rip_act_stats(rip_handle* h, const float* lidar_dev, int channels_last, int 
   return plan_stats_impl(h, h->z, plan, B, 1, q_dev, stats_dev, stream);
 }
 
+int rip_sample_normal(uint64_t seed, uint64_t first_id, int64_t n, float* out_dev, rip_stream_t stream) {
+  REQUIRE(n >= 0 && n <= 0x3fffffffLL, "n=%lld outside [0, 2^30)", (long long)n);
+  REQUIRE(n == 0 || out_dev != nullptr, "out_dev is NULL");
+  if (n == 0) return RIP_OK;
+  HIP_TRY(launch_sample_normal(seed, first_id, n, out_dev, (hipStream_t)stream));
+  return RIP_OK;
+}
+
+int rip_predict(rip_handle* h, const float* z_dev, const float* goal_dev, int G, float epsilon, const float* target_dev,
+                const float* noise_dev, uint64_t seed, int64_t row0, int B, int S, int top_k, int algorithm,
+                float* y_all_dev, float* q_dev, float* stats_dev, float* loss_all_dev, float* y_top_dev,
+                float* loss_top_dev, int32_t* index_top_dev, float* ade_dev, float* fde_dev, rip_stream_t stream) {
+  int rc = check_models(h, 0, h ? h->K : 1);
+  if (rc != RIP_OK) return rc;
+  const int K = h->K;
+  REQUIRE(z_dev != nullptr, "z_dev is NULL");
+  REQUIRE(y_all_dev != nullptr && q_dev != nullptr && stats_dev != nullptr, "y_all_dev, q_dev or stats_dev is NULL");
+  REQUIRE(y_top_dev != nullptr && loss_top_dev != nullptr && index_top_dev != nullptr,
+          "y_top_dev, loss_top_dev or index_top_dev is NULL");
+  REQUIRE(K <= MAX_MODELS, "K=%d above %d models", K, MAX_MODELS);
+  REQUIRE(B >= 1, "bad batch B=%d", B);
+  REQUIRE(S >= 1, "S=%d: at least one sample per member", S);
+  REQUIRE((long long)K * S <= 4096, "M = K S = %d x %d above 4096 candidates per observation", K, S);
+  const int M = K * S;
+  REQUIRE(top_k >= 1 && top_k <= (M < 64 ? M : 64), "top_k=%d outside [1, min(M=%d, 64)]", top_k, M);
+  REQUIRE((long long)B * M <= 0x7fffffffLL, "B M = %d x %d above 2^31 - 1 candidates", B, M);
+  REQUIRE(row0 >= 0, "row0=%lld is negative", (long long)row0);
+  REQUIRE(algorithm == RIP_ALGO_WCM || algorithm == RIP_ALGO_MA || algorithm == RIP_ALGO_BCM, "unknown algorithm %d", algorithm);
+  REQUIRE(goal_dev == nullptr || (G >= 1 && G <= MAX_GOALS && epsilon > 0.f), "bad goal arguments G=%d (1..%d) eps=%g", G,
+          MAX_GOALS, epsilon);
+  REQUIRE(target_dev != nullptr || (ade_dev == nullptr && fde_dev == nullptr), "ade_dev / fde_dev without target_dev");
+  ENTER(h, stream);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(launch_sample_forward(h->flow_w, K, z_dev, noise_dev, seed, (unsigned long long)row0, B, S, y_all_dev, s));
+  HIP_TRY(launch_ensemble_stats(h->flow_w, K, z_dev, y_all_dev, B, M, q_dev, stats_dev, s));
+  HIP_TRY(launch_rank(stats_dev, y_all_dev, goal_dev, target_dev, B, M, G, epsilon, algorithm, top_k, loss_all_dev, y_top_dev,
+                      loss_top_dev, index_top_dev, ade_dev, fde_dev, s));
+  return RIP_OK;
+}
+
 static int fill_mp(rip_handle* h, MpArgs& a, int k_fwd, int k_begin, int k_count, int first_is_fwd, const float* z_fwd,
                    const float* z, const float* goal, int B, int N, int G, int K, int algorithm, float lr, float eps,
                    int step) {

@@ -714,3 +714,48 @@ def score_cache(agent, data: "DeviceCache", batch_size: int) -> dict:
     q[i0:i0 + m].copy_(qv.t())
   torch.cuda.synchronize(dev)
   return dict(q=q.cpu().numpy(), stats=stats.cpu().numpy())
+
+
+def predict_cache(agent, data: "DeviceCache", batch_size: int, num_samples: int, top_k: int, seed: int = 0) -> dict:
+  """Open-loop evaluation of the ensemble over a whole device-resident cache, one pass: per batch of rows [i0, i0 + m)
+  `data.batch(rows, 4)` gives the transformed visual features, vec and the expert's future as the target, `rip_encode`
+  the z of the K members of `agent` (a `RIPAgent` with `max_batch >= batch_size`), and `rip_predict` with `row0 = i0`
+  draws `num_samples` trajectories per member, ranks all K x num_samples of them by the agent's algorithm (no goal) and
+  measures the best `top_k` against the expert.  Sample ids are counted from the row's index in the cache, so the
+  result does not depend on `batch_size` (a rank that takes `distributed.shard_range` of the rows passes nothing else).
+  -> dict(ade, fde, loss [n,k] float32, member [n,k] int32 best-first per row, and the data-set means
+  min_ade_1, min_ade_k, min_fde_1, min_fde_k: floats)."""
+  from oatomobile_amd import _lib, arch, prediction
+  dev = agent._device
+  if data.device != dev:
+    raise RuntimeError("predict_cache: the cache is on %s, the agent on %s" % (data.device, dev))
+  if data.channels != agent._in_channels:
+    raise ValueError("predict_cache: the cache has %d BEV channels, the agent expects %d" % (data.channels, agent._in_channels))
+  batch_size = int(batch_size)
+  if batch_size < 1 or batch_size > agent._max_batch:
+    raise ValueError("predict_cache: batch_size %d outside [1, max_batch=%d]" % (batch_size, agent._max_batch))
+  n, K = len(data), len(agent._models)
+  S, top_k = agent._check_predict("predict_cache", batch_size, num_samples, top_k, None, None, None, 0, seed)
+  if agent._sync_weights():
+    agent._online = {}
+  h = agent._handle
+  f32 = dict(device=dev, dtype=torch.float32)
+  ade, fde, loss = (torch.empty((n, top_k), **f32) for _ in range(3))
+  member = torch.empty((n, top_k), device=dev, dtype=torch.int32)
+  z = torch.empty((K, batch_size, 64), **f32)
+  agent._eager_pending = True
+  for i0 in range(0, n, batch_size):
+    m = min(batch_size, n - i0)
+    batch = data.batch(torch.arange(i0, i0 + m, device=dev), arch.T)
+    vec = torch.cat((batch["velocity"], batch["is_at_traffic_light"], batch["traffic_light_state"]), dim=1)  # [m,5]
+    zb = z.view(-1)[:K * m * 64].view(K, m, 64)
+    _lib.check(_lib.load().rip_encode(h.raw, _lib.ptr(batch["visual_features"]), _lib.ptr(vec), m, 0, K, agent._enc_dtype,
+                                      _lib.ptr(zb), None, h.stream()))
+    p = agent._predict(zb, m, S, top_k, None, batch["player_future"], None, seed, i0, False)
+    ade[i0:i0 + m], fde[i0:i0 + m], loss[i0:i0 + m], member[i0:i0 + m] = p.ade, p.fde, p.loss, p.member
+  torch.cuda.synchronize(dev)
+  out = dict(ade=ade.cpu().numpy(), fde=fde.cpu().numpy(), loss=loss.cpu().numpy(), member=member.cpu().numpy())
+  for name in ("ade", "fde"):
+    for tag, k in (("1", 1), ("k", top_k)):  # means in float64 of the float32 rows
+      out["min_%s_%s" % (name, tag)] = float(prediction.min_over_k(out[name], k).astype(np.float64).mean()) if n else float("nan")
+  return out

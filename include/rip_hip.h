@@ -359,8 +359,25 @@ int rip_predict(rip_handle* h, const float* z_dev, const float* goal_dev, int G,
  *   Any B in [1, max_batch] (batch statistics of one observation are defined: the smallest map is 4 x 4).
  * rip_train_adam: torch.optim.Adam step `step` (1-based) on the entries with trainable_dev[i] != 0
  *   (rip_train_trainable_mask: everything but the running statistics); weight_decay is added to the gradient.
- * Both enqueue on `stream` without synchronising; rip_train_create / _destroy / _trainable_mask are setup calls. */
+ * Both enqueue on `stream` without synchronising; rip_train_create / _destroy / _trainable_mask / _set_option are
+ * setup calls.
+ *
+ * rip_train_set_option(t, RIP_TRAIN_OPT_DETERMINISTIC, 1): the deterministic mode of a DIM or CIL trainer (off when
+ *   the trainer is created).  By default three kernels of the step add partial sums with float atomics (the split-K
+ *   GEMMs, the stem's and the depthwise convolutions' weight gradients), so two runs of one step differ in the last
+ *   bits.  With the mode on they store their partial sums into a table the trainer owns (about 25 MB, allocated by
+ *   this call and freed by value 0) and a second kernel adds its rows in an order fixed by the shapes.
+ *   GUARANTEED: rip_train_forward_backward / rip_cil_train_forward_backward (with or without gradients) and
+ *   rip_train_adam write the same bits on every run, in every trainer and every process, for the same inputs
+ *   (parameters, moments, batch, target, dropout mask, step), the same B and the same device model.
+ *   NOT guaranteed: equal bits across different B (the split of a reduction follows the shapes), across device models,
+ *   or after anything the caller does to the gradients in between whose order it does not control (a data-parallel
+ *   all-reduce's order belongs to the collective library).  The mode's sums are taken in another order than the
+ *   default's: the two agree to fp32 rounding, not bit for bit.
+ *   RIP_EINVAL for a NULL trainer, an unknown option, or a value other than 0 / 1. */
 typedef struct rip_trainer rip_trainer;
+#define RIP_TRAIN_OPT_DETERMINISTIC 1
+int rip_train_set_option(rip_trainer* t, int option, int value);
 size_t rip_train_numel(int in_channels);
 int rip_train_create(rip_trainer** out, int in_channels, int max_batch, int device);
 int rip_train_destroy(rip_trainer* t);

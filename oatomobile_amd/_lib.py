@@ -85,6 +85,7 @@ SIGNATURES = [
     ("rip_train_numel", c_size_t, [c_int]),
     ("rip_train_create", c_int, [POINTER(c_void_p), c_int, c_int, c_int]),
     ("rip_train_destroy", c_int, [c_void_p]),
+    ("rip_train_set_option", c_int, [c_void_p, c_int, c_int]),
     ("rip_train_trainable_mask", c_int, [c_void_p, c_void_p, c_size_t]),
     ("rip_train_forward_backward", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -110,6 +111,7 @@ OPT_SEARCH_KERNEL, OPT_ENCODER_FUSED, OPT_SEARCH_REGROUP, OPT_ENCODER_MEGA, OPT_
 OPT_ENCODER_VARIANT, OPT_KERNEL_LOG = 5, 6
 ENC_VAR_IRB_ROUND3, ENC_VAR_FRONT_ROUND3, ENC_VAR_ROWS_F5_7, ENC_VAR_F17_LAYERWISE = 1, 2, 4, 8
 ENC_VAR_FP32_LAYERWISE = 16  # fp32 encoder without the split-f16 tile blocks (encoder_split_tile.hip)
+TRAIN_OPT_DETERMINISTIC = 1  # RIP_TRAIN_OPT_DETERMINISTIC of include/rip_hip.h (rip_train_set_option)
 STAT_MEAN, STAT_VARIANCE, STAT_MIN, STAT_MAX, STAT_SLOTS = 0, 1, 2, 3, 4  # RIP_STAT_* of include/rip_hip.h
 SEARCH_KERNELS = {"auto": 0, "chain": 1, "phase": 3, "split": 4, "pair": 5}  # "pair": split-f16, paired workgroup shape forced
 

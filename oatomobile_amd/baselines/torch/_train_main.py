@@ -40,6 +40,9 @@ def parse_args(kind: str, argv=None) -> argparse.Namespace:
   p.add_argument("--cache_dir", default=None, help="Packed caches of train/ and val/ (default <output_dir>/cache); "
                  "reused while they match the datum files.")
   p.add_argument("--seed", type=int, default=0, help="Seeds the initial weights and the epoch generator.")
+  p.add_argument("--deterministic", action="store_true", default=False,
+                 help="Fixed-order sums in the training step: the same --seed, data, batch size and device model give "
+                 "the same bits on every run (a little slower; DESIGN.md section 4.3g).")
   args = p.parse_args(argv)
   if kind == "dim" and args.num_timesteps_to_keep != 4:
     p.error("the DIM model is built for num_timesteps_to_keep=4 only (ImitativeModel(output_shape=(4, 2))); got %d" %
@@ -118,11 +121,11 @@ def main(kind: str, argv=None) -> int:
   if kind == "dim":
     model = ImitativeModel.synthetic(args.seed, in_channels=C).to(device)
     trainer = DIMTrainer(model, lr=args.learning_rate, weight_decay=args.weight_decay, noise_level=NOISE_LEVEL,
-                         max_batch=args.batch_size, device=device)
+                         max_batch=args.batch_size, device=device, deterministic=args.deterministic)
   else:
     model = BehaviouralModel.synthetic(args.seed, in_channels=C, output_shape=(T, 2)).to(device)
     trainer = CILTrainer(model, lr=args.learning_rate, weight_decay=args.weight_decay, max_batch=args.batch_size,
-                         device=device)
+                         device=device, deterministic=args.deterministic)
   gen = torch.Generator(device=device).manual_seed(args.seed)
   extra = {"nll_limit": nll_limit(T)} if kind == "dim" else {}
   with open(os.path.join(log_dir, "metrics.jsonl"), "a") as log:

@@ -1117,6 +1117,18 @@ int rip_train_destroy(rip_trainer* t) {
   return RIP_OK;
 }
 
+int rip_train_set_option(rip_trainer* t, int option, int value) {
+  REQUIRE(t != nullptr, "trainer is NULL");
+  REQUIRE(option == RIP_TRAIN_OPT_DETERMINISTIC, "unknown trainer option %d", option);
+  REQUIRE(value == 0 || value == 1, "RIP_TRAIN_OPT_DETERMINISTIC takes 0 or 1, got %d", value);
+  Trainer* tr = reinterpret_cast<Trainer*>(t);
+  DeviceScope scope(trainer_device(tr));
+  if (scope.err != hipSuccess) return fail(RIP_EHIP, "hipSetDevice failed: %s", hipGetErrorString(scope.err));
+  hipError_t e = trainer_set_deterministic(tr, value);
+  if (e != hipSuccess) return fail(RIP_EHIP, "deterministic-mode workspace: %s", hipGetErrorString(e));
+  return RIP_OK;
+}
+
 int rip_train_trainable_mask(const rip_trainer* t, unsigned char* mask_host, size_t numel) {
   REQUIRE(t != nullptr && mask_host != nullptr, "NULL argument");
   const Trainer* tr = reinterpret_cast<const Trainer*>(t);

@@ -22,6 +22,9 @@ size_t cil_train_numel(int in_channels);
 hipError_t trainer_create(Trainer** out, int in_channels, int max_batch, int device, int cil_T = 0);
 int trainer_cil_horizon(const Trainer* t);  // 0 for a DIM trainer
 void trainer_destroy(Trainer* t);
+// deterministic mode (rip_train_set_option): on allocates the partial-sum workspace, off frees it; DIM and CIL alike
+hipError_t trainer_set_deterministic(Trainer* t, int on);
+int trainer_deterministic(const Trainer* t);
 size_t trainer_numel(const Trainer* t);
 int trainer_max_batch(const Trainer* t);
 int trainer_device(const Trainer* t);

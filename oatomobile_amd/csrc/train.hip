@@ -21,6 +21,10 @@
 //   flow_train_kernel   (flow.hip) teacher-forced inverse, its adjoint through all 4 steps into z, and the per-step gate
 //                       gradients whose outer products with the saved inputs are the GRU / head weight gradients (GEMMs)
 //   adam_kernel         torch.optim.Adam defaults, skipping the running statistics
+// Deterministic mode (trainer_set_deterministic): the three places that add with float atomics (the
+// split-K GEMM, stem_wgrad, dw_wgrad) store their partial sums into a trainer-owned table instead, and
+// part_reduce_kernel adds the table's rows in a fixed order — the same bits on every run.  Off by default: the default
+// launches and their kernels are unchanged.
 // Parity with the reference's step: tests/golden/g15.  The kernels are one tuning pass beyond the first correct path
 // (48.7 -> 11 ms per 128-observation step); the step is still one launch per layer and operation.
 #include <hip/hip_runtime.h>
@@ -59,6 +63,14 @@ __device__ __forceinline__ float q4_sum(float x) {
   return __uint_as_float(t[0]) + __uint_as_float(t[1]);
 }
 constexpr float BN_EPS = 1e-5f, BN_MOMENTUM = 0.1f;
+// the deterministic mode's partial table (Trainer::det); ws == nullptr: the mode is off
+struct DetWs {
+  float* ws = nullptr;
+  size_t floats = 0;
+};
+// A split GEMM has fewer than 512 output tiles of 4096 elements (256x16, 128x32 or 64x64) and at most
+// ceil(1024 / tiles) splits: splits * M * N <= (1024 + tiles - 1) * 4096 < 1534 * 4096 floats (25 MB), whatever the batch.
+constexpr size_t DET_GEMM_FLOATS = (size_t)1534 * 4096;
 
 // ------------------------------------------------------------------------------------------------------------
 // GEMM: C[M,N] (ldc) (+)= op(A)[M,K] op(B)[K,N];  TA: A is stored [K,M]; TB: B is stored [N,K].
@@ -67,8 +79,10 @@ constexpr float BN_EPS = 1e-5f, BN_MOMENTUM = 0.1f;
 // chunks of BK through double-buffered LDS tiles [k][m] / [k][n]; the next chunk's global loads (16-byte when the
 // operand's contiguous dimension allows: VEC) are in flight while the current one is multiplied, one barrier per chunk.
 // gridDim.z > 1: split-K, partial sums added with atomics (C zeroed by the caller); accumulate: C += (no split).
+// DET (deterministic mode, launched with gridDim.z > 1 only): C is the partial table [gridDim.z][M][N]; split z stores its
+// tile into slab z with plain stores, and part_reduce_kernel adds the slabs (and the old C of an accumulating call).
 // ------------------------------------------------------------------------------------------------------------
-template <bool TA, bool TB, int BM, int BN, int BK, int WR, bool VEC>
+template <bool TA, bool TB, int BM, int BN, int BK, int WR, bool VEC, bool DET = false>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B,
                                                        int ldb, float* __restrict__ C, int ldc, int M, int N, int K,
                                                        int kchunk, int accumulate) {
@@ -208,7 +222,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
   // result tile: lane (n, q), register r <-> row 4 q + r, column n.  `accumulate` (no split): the old values are added
   // in a first pass of unconditional loads from clamped addresses — inside the per-element branch below each load was
   // waited for on its own (16 memory round trips in sequence per thread)
-  if (accumulate && gridDim.z == 1) {
+  if (!DET && accumulate && gridDim.z == 1) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -227,19 +241,63 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
       for (int r = 0; r < 4; ++r) {
         const int gm = m0 + wm + i * 16 + 4 * q + r, gn = n0 + wn + j * 16 + n;
         if (gm < M && gn < N) {
-          float* p = C + (size_t)gm * ldc + gn;
-          if (gridDim.z > 1)
-            atomicAdd(p, acc[i][j][r]);
-          else
-            *p = acc[i][j][r];
+          if (DET) {
+            C[((size_t)blockIdx.z * M + gm) * N + gn] = acc[i][j][r];
+          } else {
+            float* p = C + (size_t)gm * ldc + gn;
+            if (gridDim.z > 1)
+              atomicAdd(p, acc[i][j][r]);
+            else
+              *p = acc[i][j][r];
+          }
         }
       }
 }
 
+// Second stage of the deterministic mode's three reductions: part is a table [rows][n] of partial sums written with plain
+// stores, and   out[(i / N) * ldo + i % N] = (accumulate ? its old value : 0) + sum_r part[r][i],  i < n   (N = n, ldo = n:
+// a plain vector; the GEMM's C is n = M * N entries with row pitch ldo).  A block owns 32 columns, its RL row lanes
+// walk rows rl, rl + RL, ... in that order, and lane 0 adds the old value and then the RL lane sums, lane 0 first.  The
+// order depends on (rows, RL) alone, i.e. on the shapes; with rows <= RL it is old + p_0 + p_1 + ... + p_{rows-1}.
+template <int RL>
+__global__ __launch_bounds__(32 * RL) void part_reduce_kernel(const float* __restrict__ part, int rows, int n, int N,
+                                                               float* __restrict__ out, int ldo, int accumulate) {
+  __shared__ float sm[RL][32];
+  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
+  const int i = (int)blockIdx.x * 32 + cl;
+  float s = 0.f;
+  if (i < n) {
+#pragma unroll 8
+    for (int r = rl; r < rows; r += RL) s += part[(size_t)r * n + i];
+  }
+  sm[rl][cl] = s;
+  __syncthreads();
+  if (rl == 0 && i < n) {
+    float* o = out + (size_t)(i / N) * ldo + i % N;
+    float t = accumulate ? *o : 0.f;
+#pragma unroll
+    for (int g = 0; g < RL; ++g) t += sm[g][cl];
+    *o = t;
+  }
+}
+void part_reduce(const float* part, int rows, int n, int N, float* out, int ldo, int accumulate, hipStream_t s) {
+  const dim3 grid((unsigned)((n + 31) / 32));
+  if (rows > 32)
+    hipLaunchKernelGGL(part_reduce_kernel<32>, grid, dim3(1024), 0, s, part, rows, n, N, out, ldo, accumulate);
+  else
+    hipLaunchKernelGGL(part_reduce_kernel<8>, grid, dim3(256), 0, s, part, rows, n, N, out, ldo, accumulate);
+}
+
 template <bool TA, bool TB, int BM, int BN, int BK, int WR>
-void gemm_launch(bool vec, dim3 grid, hipStream_t s, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+void gemm_launch(bool vec, bool det, dim3 grid, hipStream_t s, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                  int M, int N, int K, int kchunk, int accumulate) {
-  if (vec)
+  if (det && vec)
+    hipLaunchKernelGGL((gemm_f32_kernel<TA, TB, BM, BN, BK, WR, true, true>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M,
+                       N, K, kchunk, accumulate);
+  else if (det)
+    hipLaunchKernelGGL((gemm_f32_kernel<TA, TB, BM, BN, BK, WR, false, true>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M,
+                       N, K, kchunk, accumulate);
+  else if (vec)
     hipLaunchKernelGGL((gemm_f32_kernel<TA, TB, BM, BN, BK, WR, true>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, N,
                        K, kchunk, accumulate);
   else
@@ -248,18 +306,20 @@ void gemm_launch(bool vec, dim3 grid, hipStream_t s, const float* A, int lda, co
 }
 
 template <bool TA, bool TB>
-void gemm_shape(bool vec, int bn_sel, dim3 grid, hipStream_t s, const float* A, int lda, const float* B, int ldb, float* C,
+void gemm_shape(bool vec, bool det, int bn_sel, dim3 grid, hipStream_t s, const float* A, int lda, const float* B, int ldb, float* C,
                 int ldc, int M, int N, int K, int kchunk, int accumulate) {
   if (bn_sel == 16)
-    gemm_launch<TA, TB, 256, 16, 16, 4>(vec, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
+    gemm_launch<TA, TB, 256, 16, 16, 4>(vec, det, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
   else if (bn_sel == 32)
-    gemm_launch<TA, TB, 128, 32, 32, 4>(vec, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
+    gemm_launch<TA, TB, 128, 32, 32, 4>(vec, det, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
   else
-    gemm_launch<TA, TB, 64, 64, 32, 2>(vec, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
+    gemm_launch<TA, TB, 64, 64, 32, 2>(vec, det, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
 }
 
+// det.ws != nullptr: deterministic mode — a split call stores its partial tiles into det.ws [splits][M][N] and
+// part_reduce adds them; the split itself (splits, kchunk) is the default path's, a function of the shapes alone
 hipError_t gemm(bool ta, bool tb, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N,
-                int K, int accumulate, hipStream_t s) {
+                int K, int accumulate, hipStream_t s, const DetWs& det) {
   if (M <= 0 || N <= 0 || K <= 0) return hipSuccess;
   // block shape by the narrow side; wide-and-short outputs (M small, N large) keep the square block
   const int bn = (N <= 16 && M >= 256) ? 16 : ((N <= 32 && M >= 128) ? 32 : 64);
@@ -269,6 +329,7 @@ hipError_t gemm(bool ta, bool tb, const float* A, int lda, const float* B, int l
   // reductions over B*H*W with few output tiles: split K so that the chip has work (C must then be pre-zeroed or
   // hold the value to add to: atomics add into it)
   const long tiles = (long)grid.x * grid.y;
+  bool det_split = false;
   // (weight gradients, `ta`: from K = 1024 — the 4x4 stage's K = 2048 with 45-100 output tiles ran as that many
   // workgroups of 64 serial chunks, 68 us a layer)
   // forward / input gradients of the same stage (M = 2048 rows, 96 output tiles, K = 960: 30 serial chunks, 35-45 us):
@@ -280,7 +341,15 @@ hipError_t gemm(bool ta, bool tb, const float* A, int lda, const float* B, int l
     if (splits > 1) {
       kchunk = ((K + splits - 1) / splits + bk - 1) / bk * bk;
       grid.z = (K + kchunk - 1) / kchunk;
-      if (!accumulate) {
+      if (det.ws != nullptr) {
+        // (DET_GEMM_FLOATS bounds every split call's table; one that still does not fit runs unsplit: plain stores)
+        if (grid.z > 1 && (size_t)grid.z * M * N <= det.floats) {
+          det_split = true;
+        } else {
+          kchunk = (K + bk - 1) / bk * bk;
+          grid.z = 1;
+        }
+      } else if (!accumulate) {
         hipError_t e = hipMemset2DAsync(C, (size_t)ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, s);
         if (e != hipSuccess) return e;
       }
@@ -296,14 +365,17 @@ hipError_t gemm(bool ta, bool tb, const float* A, int lda, const float* B, int l
   const size_t b_bytes = ((size_t)((tb ? N : K) - 1) * ldb + (tb ? K : N)) * sizeof(float);
   const bool vec = lda % 4 == 0 && ldb % 4 == 0 && al16(A) && al16(B) && (ta ? M % 4 == 0 : K % 4 == 0) &&
                    (tb ? K % 4 == 0 : N % 4 == 0) && a_bytes < (size_t)GEMM_OOB && b_bytes < (size_t)GEMM_OOB;
+  float* Cw = det_split ? det.ws : C;
+  const int ldw = det_split ? N : ldc, acc_k = det_split ? 0 : accumulate;
   if (ta && tb)
-    gemm_shape<true, true>(vec, bn, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
+    gemm_shape<true, true>(vec, det_split, bn, grid, s, A, lda, B, ldb, Cw, ldw, M, N, K, kchunk, acc_k);
   else if (ta)
-    gemm_shape<true, false>(vec, bn, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
+    gemm_shape<true, false>(vec, det_split, bn, grid, s, A, lda, B, ldb, Cw, ldw, M, N, K, kchunk, acc_k);
   else if (tb)
-    gemm_shape<false, true>(vec, bn, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
+    gemm_shape<false, true>(vec, det_split, bn, grid, s, A, lda, B, ldb, Cw, ldw, M, N, K, kchunk, acc_k);
   else
-    gemm_shape<false, false>(vec, bn, grid, s, A, lda, B, ldb, C, ldc, M, N, K, kchunk, accumulate);
+    gemm_shape<false, false>(vec, det_split, bn, grid, s, A, lda, B, ldb, Cw, ldw, M, N, K, kchunk, acc_k);
+  if (det_split) part_reduce(det.ws, (int)grid.z, M * N, N, C, ldc, accumulate, s);
   return hipGetLastError();
 }
 
@@ -421,6 +493,68 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
   for (int i = threadIdx.x; i < Co * taps; i += 256) atomicAdd(&dw[i], sm[i]);
 }
 
+// Deterministic mode: the same per-thread sums, then no atomics — the threads park their sums in LDS (36 taps a round),
+// thread (oc, tap) adds the `groups` pixel lanes of its output in ascending order and stores the block's total into row
+// blockIdx.x of the partial table part[blocks][Co * C * 9]; part_reduce_kernel adds the rows.  Co <= 64 like above.
+template <int CMAX>
+__global__ __launch_bounds__(256) void stem_wgrad_det_kernel(const float* __restrict__ in, const float* __restrict__ dpre,
+                                                             float* __restrict__ part, int B, int C, int Hin, int Ho, int Co,
+                                                             int pix_per_block) {
+  constexpr int ROUND = 36;
+  static_assert(CMAX * 9 % ROUND == 0, "taps per round");
+  __shared__ float park[ROUND][256];
+  const int taps = C * 9;
+  const size_t npix = (size_t)B * Ho * Ho;
+  const size_t p0 = (size_t)blockIdx.x * pix_per_block;
+  const size_t p1 = p0 + pix_per_block < npix ? p0 + pix_per_block : npix;
+  const int groups = 256 / Co;
+  const int oc = threadIdx.x % Co, sub = threadIdx.x / Co;
+  // the thread's sums over pixels p0 + sub, p0 + sub + groups, ... as in stem_wgrad_kernel (a thread past the last whole
+  // pixel lane, 256 % Co != 0, walks none); a channel past C is skipped under a uniform test, not a `break`, so that
+  // the channel loop unrolls and acc[] stays in registers for every CMAX
+  float acc[CMAX * 9];
+#pragma unroll
+  for (int t = 0; t < CMAX * 9; ++t) acc[t] = 0.f;
+  for (size_t p = sub < groups ? p0 + sub : p1; p < p1; p += groups) {
+    const int ox = p % Ho, oy = (p / Ho) % Ho, b = p / ((size_t)Ho * Ho);
+    const float g = dpre[p * Co + oc];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+      if (c < C) {
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+          const int iy = 2 * oy - 1 + ky;
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) {
+            const int ix = 2 * ox - 1 + kx;
+            const bool ok = (unsigned)iy < (unsigned)Hin && (unsigned)ix < (unsigned)Hin;  // clamped load + select: no branch
+            const float v = in[(((size_t)b * C + c) * Hin + min(max(iy, 0), Hin - 1)) * Hin + min(max(ix, 0), Hin - 1)];
+            acc[c * 9 + ky * 3 + kx] = fmaf(g, ok ? v : 0.f, acc[c * 9 + ky * 3 + kx]);
+          }
+        }
+      }
+    }
+  }
+  float* row = part + (size_t)blockIdx.x * Co * taps;
+#pragma unroll
+  for (int t0 = 0; t0 < CMAX * 9; t0 += ROUND) {
+    if (t0 < taps) {  // the same for every thread of the block
+#pragma unroll
+      for (int t = 0; t < ROUND; ++t) park[t][threadIdx.x] = acc[t0 + t];
+      __syncthreads();
+      for (int i = threadIdx.x; i < Co * ROUND; i += 256) {
+        const int o = i % Co, t = i / Co;
+        if (t0 + t < taps) {
+          float v = 0.f;
+          for (int g = 0; g < groups; ++g) v += park[t][g * Co + o];
+          row[o * taps + t0 + t] = v;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // depthwise: x NHWC [B,Hi,Hi,C] -> out [B,Ho,Ho,C]; w [C][3][3]
 // thread = (pixel, 4 channels): 16-byte activation accesses; per element the FMA chain runs over (ky, kx) ascending
 __device__ __forceinline__ float4 dw_taps4(const float* __restrict__ w, int c4, int t) {
@@ -532,7 +666,9 @@ __global__ void dw_dgrad_kernel(const float* __restrict__ dpre, const float* __r
 // 50x50 / 25x25 maps several bands per observation.  (History: a first version walked pixel chunks with scalar loads
 // and a div / mod per pixel — 289 us per layer, 4.9 ms of a 26 ms step; an (observation, band) x all-channels version
 // ended every block in C * 9 atomics after 36 LDS atomics per item.)
-template <int STRIDE>
+// DET (deterministic mode): dw is the partial table [gridDim.y][C * 9]; the block stores its 64 * 9 sums into row
+// blockIdx.y with plain stores (every row is written in full) and part_reduce_kernel adds the rows.
+template <int STRIDE, bool DET = false>
 __global__ __launch_bounds__(256) void dw_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dpre,
                                                        float* __restrict__ dw, int B, int C, int Hi, int Ho, int G, int bands) {
   __shared__ float sm[4][64 * 9];  // one row per wave: added in a fixed order at the end, no LDS atomics
@@ -619,7 +755,11 @@ __global__ __launch_bounds__(256) void dw_wgrad_kernel(const float* __restrict__
   __syncthreads();
   for (int i = threadIdx.x; i < 64 * 9; i += 256) {
     const int ch = (int)blockIdx.x * 64 + i / 9;
-    if (ch < C) atomicAdd(&dw[(size_t)ch * 9 + i % 9], ((sm[0][i] + sm[1][i]) + sm[2][i]) + sm[3][i]);
+    if (DET) {
+      if (ch < C) dw[((size_t)blockIdx.y * C + ch) * 9 + i % 9] = ((sm[0][i] + sm[1][i]) + sm[2][i]) + sm[3][i];
+    } else {
+      if (ch < C) atomicAdd(&dw[(size_t)ch * 9 + i % 9], ((sm[0][i] + sm[1][i]) + sm[2][i]) + sm[3][i]);
+    }
   }
 }
 
@@ -1101,6 +1241,7 @@ struct Trainer {
   float* tail = nullptr;  // pooled, feat/merged, h1, h2, z and their gradients
   float* flowbuf = nullptr;  // decoder records: DIM flow (B rows + the relaid blob) or CIL (B * cil_T rows)
   size_t max_act = 0, stats_floats = 0, partial_floats = 0;
+  DetWs det;  // deterministic mode: the partial table of the split GEMMs, stem_wgrad and dw_wgrad (one at a time)
 };
 
 static size_t round4(size_t n) { return n; }
@@ -1240,11 +1381,44 @@ hipError_t trainer_create(Trainer** out, int in_channels, int max_batch, int dev
   return hipSuccess;
 }
 
+// deterministic mode's stem_wgrad: chunks of at least 512 pixels (the default's), and at most 513 blocks, so that the
+// second stage has a few hundred rows to add however large the batch
+static int stem_det_ppb(size_t M) { return (int)std::max<size_t>(512, (M + 511) / 512); }
+
+// Switches the deterministic mode: on allocates the partial table, off frees it (setup call: hipFree synchronises).
+// The table is sized for the largest of
+//   split GEMM   DET_GEMM_FLOATS (a bound for every shape)
+//   stem_wgrad   at most 513 blocks x cout * cin * 9
+//   dw_wgrad     grid.y x C * 9 <= (grid.y x chunks) x 576 with grid.y x chunks <= max(1024 + chunks, (B / 8 + 1) x chunks)
+//                and chunks <= 15 (encoder_backward's launch shape): (1039 + 2 max_batch) x 576
+// and every launch checks its own need against it before it runs.
+hipError_t trainer_set_deterministic(Trainer* t, int on) {
+  if (!on) {
+    hipError_t e = hipSuccess;
+    if (t->det.ws != nullptr) e = hipFree(t->det.ws);
+    t->det = DetWs();
+    return e;
+  }
+  if (t->det.ws != nullptr) return hipSuccess;
+  size_t need = DET_GEMM_FLOATS;
+  for (const Layer& l : t->plan.layers)
+    if (l.kind == L_STEM) need = std::max(need, (size_t)513 * l.cout * l.cin * 9);
+  need = std::max(need, ((size_t)1039 + 2 * (size_t)t->max_batch) * 576);
+  float* p = nullptr;
+  hipError_t e = hipMalloc((void**)&p, need * sizeof(float));
+  if (e != hipSuccess) return e;
+  t->det.ws = p;
+  t->det.floats = need;
+  return hipSuccess;
+}
+int trainer_deterministic(const Trainer* t) { return t->det.ws != nullptr ? 1 : 0; }
+
 void trainer_destroy(Trainer* t) {
   if (t == nullptr) return;
   float* ptrs[] = {t->pre, t->post, t->dpost, t->gbuf, t->dpre, t->stats, t->sums, t->partial, t->tail, t->flowbuf};
   for (float* p : ptrs)
     if (p != nullptr) (void)hipFree(p);
+  if (t->det.ws != nullptr) (void)hipFree(t->det.ws);
   delete t;
 }
 
@@ -1339,7 +1513,7 @@ static hipError_t encoder_forward(StepCtx& c) {
       hipLaunchKernelGGL(dw_fwd_kernel, dim3(nblk(total / 4)), dim3(256), 0, s, x, params + q.w, pre, B, l.cout, l.h_in, l.h_out,
                          l.stride);
     } else {
-      TRY(gemm(false, true, x, l.cin, params + q.w, l.cin, pre, l.cout, (int)M, l.cout, l.cin, 0, s));
+      TRY(gemm(false, true, x, l.cin, params + q.w, l.cin, pre, l.cout, (int)M, l.cout, l.cin, 0, s, t->det));
     }
     float* mean = t->stats + st_off;
     float* invstd = mean + l.cout;
@@ -1385,14 +1559,14 @@ static hipError_t head_forward(StepCtx& c, const float* vec) {
   float* zz = c.zz;
   hipLaunchKernelGGL(pool_drop_fwd_kernel, dim3(nblk(Bz * LAST_C)), dim3(256), 0, s, A(t->post, nl - 1), dropout_mask, pooled,
                      B, P, LAST_C);
-  TRY(gemm(false, true, pooled, LAST_C, params + t->cls_w, LAST_C, merged, NIN, B, FEAT, LAST_C, 0, s));
+  TRY(gemm(false, true, pooled, LAST_C, params + t->cls_w, LAST_C, merged, NIN, B, FEAT, LAST_C, 0, s, t->det));
   hipLaunchKernelGGL(bias_act_kernel, dim3(nblk(Bz * FEAT)), dim3(256), 0, s, merged, NIN, params + t->cls_b, B, FEAT, 0);
   hipLaunchKernelGGL(copy_cols_kernel, dim3(nblk(Bz * t->vec_w)), dim3(256), 0, s, vec, t->vec_w, merged + FEAT, NIN, B, t->vec_w);
-  TRY(gemm(false, true, merged, NIN, params + t->mrg_w[0], NIN, h1, HID, B, HID, NIN, 0, s));
+  TRY(gemm(false, true, merged, NIN, params + t->mrg_w[0], NIN, h1, HID, B, HID, NIN, 0, s, t->det));
   hipLaunchKernelGGL(bias_act_kernel, dim3(nblk(Bz * HID)), dim3(256), 0, s, h1, HID, params + t->mrg_b[0], B, HID, 1);
-  TRY(gemm(false, true, h1, HID, params + t->mrg_w[1], HID, h2, HID, B, HID, HID, 0, s));
+  TRY(gemm(false, true, h1, HID, params + t->mrg_w[1], HID, h2, HID, B, HID, HID, 0, s, t->det));
   hipLaunchKernelGGL(bias_act_kernel, dim3(nblk(Bz * HID)), dim3(256), 0, s, h2, HID, params + t->mrg_b[1], B, HID, 1);
-  TRY(gemm(false, true, h2, HID, params + t->mrg_w[2], HID, zz, HID, B, HID, HID, 0, s));
+  TRY(gemm(false, true, h2, HID, params + t->mrg_w[2], HID, zz, HID, B, HID, HID, 0, s, t->det));
   hipLaunchKernelGGL(bias_act_kernel, dim3(nblk(Bz * HID)), dim3(256), 0, s, zz, HID, params + t->mrg_b[2], B, HID, 1);
   return hipSuccess;
 }
@@ -1416,17 +1590,17 @@ static hipError_t head_backward(StepCtx& c) {
   // ================================== backward ==================================
   // ---- merger / classifier ----
   hipLaunchKernelGGL(relu_bwd_colsum_kernel, dim3((HID + 31) / 32), dim3(256), 0, s, dz, zz, HID, grads + t->mrg_b[2], B, HID);
-  TRY(gemm(true, false, dz, HID, h2, HID, grads + t->mrg_w[2], HID, HID, HID, B, 0, s));
-  TRY(gemm(false, false, dz, HID, params + t->mrg_w[2], HID, dh2, HID, B, HID, HID, 0, s));
+  TRY(gemm(true, false, dz, HID, h2, HID, grads + t->mrg_w[2], HID, HID, HID, B, 0, s, t->det));
+  TRY(gemm(false, false, dz, HID, params + t->mrg_w[2], HID, dh2, HID, B, HID, HID, 0, s, t->det));
   hipLaunchKernelGGL(relu_bwd_colsum_kernel, dim3((HID + 31) / 32), dim3(256), 0, s, dh2, h2, HID, grads + t->mrg_b[1], B, HID);
-  TRY(gemm(true, false, dh2, HID, h1, HID, grads + t->mrg_w[1], HID, HID, HID, B, 0, s));
-  TRY(gemm(false, false, dh2, HID, params + t->mrg_w[1], HID, dh1, HID, B, HID, HID, 0, s));
+  TRY(gemm(true, false, dh2, HID, h1, HID, grads + t->mrg_w[1], HID, HID, HID, B, 0, s, t->det));
+  TRY(gemm(false, false, dh2, HID, params + t->mrg_w[1], HID, dh1, HID, B, HID, HID, 0, s, t->det));
   hipLaunchKernelGGL(relu_bwd_colsum_kernel, dim3((HID + 31) / 32), dim3(256), 0, s, dh1, h1, HID, grads + t->mrg_b[0], B, HID);
-  TRY(gemm(true, false, dh1, HID, merged, NIN, grads + t->mrg_w[0], NIN, HID, NIN, B, 0, s));
-  TRY(gemm(false, false, dh1, HID, params + t->mrg_w[0], NIN, dmerged, NIN, B, NIN, HID, 0, s));
-  TRY(gemm(true, false, dmerged, NIN, pooled, LAST_C, grads + t->cls_w, LAST_C, FEAT, LAST_C, B, 0, s));
+  TRY(gemm(true, false, dh1, HID, merged, NIN, grads + t->mrg_w[0], NIN, HID, NIN, B, 0, s, t->det));
+  TRY(gemm(false, false, dh1, HID, params + t->mrg_w[0], NIN, dmerged, NIN, B, NIN, HID, 0, s, t->det));
+  TRY(gemm(true, false, dmerged, NIN, pooled, LAST_C, grads + t->cls_w, LAST_C, FEAT, LAST_C, B, 0, s, t->det));
   hipLaunchKernelGGL(colsum_kernel, dim3((FEAT + 31) / 32), dim3(256), 0, s, dmerged, NIN, grads + t->cls_b, B, FEAT);
-  TRY(gemm(false, false, dmerged, NIN, params + t->cls_w, LAST_C, dpooled, LAST_C, B, LAST_C, FEAT, 0, s));
+  TRY(gemm(false, false, dmerged, NIN, params + t->cls_w, LAST_C, dpooled, LAST_C, B, LAST_C, FEAT, 0, s, t->det));
   hipLaunchKernelGGL(pool_drop_bwd_kernel, dim3(nblk(Bz * P * LAST_C)), dim3(256), 0, s, dpooled, dropout_mask,
                      A(t->dpost, nl - 1), B, P, LAST_C);
   return hipSuccess;
@@ -1485,7 +1659,17 @@ static hipError_t encoder_backward(StepCtx& c) {
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nblk(total)), dim3(256), 0, s, t->gbuf, A(t->pre, i), mean, invstd,
                        params + q.gamma, sums_b, t->dpre, total, l.cout, M, batch_stats);
     const float* x = i == 0 ? visual : A(t->post, i - 1);
-    if (l.kind == L_STEM) {
+    if (l.kind == L_STEM && t->det.ws != nullptr) {
+      const int ppb = stem_det_ppb(M), blocks = (int)nblk(M, ppb), n = l.cout * l.cin * 9;
+      if ((size_t)blocks * n > t->det.floats || l.cout > 64) return hipErrorInvalidValue;
+      if (l.cin <= 4)
+        hipLaunchKernelGGL(stem_wgrad_det_kernel<4>, dim3(blocks), dim3(256), 0, s, x, t->dpre, t->det.ws, B, l.cin, l.h_in,
+                           l.h_out, l.cout, ppb);
+      else
+        hipLaunchKernelGGL(stem_wgrad_det_kernel<16>, dim3(blocks), dim3(256), 0, s, x, t->dpre, t->det.ws, B, l.cin, l.h_in,
+                           l.h_out, l.cout, ppb);
+      part_reduce(t->det.ws, blocks, n, n, grads + q.w, n, 0, s);
+    } else if (l.kind == L_STEM) {
       const int ppb = 512;
       if (l.cin <= 4)
         hipLaunchKernelGGL(stem_wgrad_kernel<4>, dim3(nblk(M, ppb)), dim3(256), 0, s, x, t->dpre, grads + q.w, B, l.cin, l.h_in,
@@ -1502,7 +1686,17 @@ static hipError_t encoder_backward(StepCtx& c) {
       const int groups = (B + G - 1) / G;
       const int bands = std::max(1, std::min(l.h_out / 4, (int)(1024 / ((long)groups * chunks))));
       const dim3 grid(chunks, groups * bands);
-      if (l.stride == 1)
+      if (t->det.ws != nullptr) {
+        const int n = l.cout * 9;
+        if ((size_t)grid.y * n > t->det.floats) return hipErrorInvalidValue;
+        if (l.stride == 1)
+          hipLaunchKernelGGL((dw_wgrad_kernel<1, true>), grid, dim3(256), 0, s, x, t->dpre, t->det.ws, B, l.cout, l.h_in,
+                             l.h_out, G, bands);
+        else
+          hipLaunchKernelGGL((dw_wgrad_kernel<2, true>), grid, dim3(256), 0, s, x, t->dpre, t->det.ws, B, l.cout, l.h_in,
+                             l.h_out, G, bands);
+        part_reduce(t->det.ws, (int)grid.y, n, n, grads + q.w, n, 0, s);
+      } else if (l.stride == 1)
         hipLaunchKernelGGL(dw_wgrad_kernel<1>, grid, dim3(256), 0, s, x, t->dpre, grads + q.w, B, l.cout, l.h_in, l.h_out, G,
                            bands);
       else
@@ -1512,8 +1706,8 @@ static hipError_t encoder_backward(StepCtx& c) {
       hipLaunchKernelGGL(dw_dgrad_kernel, dim3(nblk(tin / 4)), dim3(256), 0, s, t->dpre, params + q.w, A(t->dpost, i - 1), B, l.cout,
                          l.h_in, l.h_out, l.stride, acc_in);
     } else {
-      TRY(gemm(true, false, t->dpre, l.cout, x, l.cin, grads + q.w, l.cin, l.cout, l.cin, (int)M, 1, s));  // grads are zero: add
-      TRY(gemm(false, false, t->dpre, l.cout, params + q.w, l.cin, A(t->dpost, i - 1), l.cin, (int)M, l.cin, l.cout, acc_in, s));
+      TRY(gemm(true, false, t->dpre, l.cout, x, l.cin, grads + q.w, l.cin, l.cout, l.cin, (int)M, 1, s, t->det));  // grads are zero: add
+      TRY(gemm(false, false, t->dpre, l.cout, params + q.w, l.cin, A(t->dpost, i - 1), l.cin, (int)M, l.cin, l.cout, acc_in, s, t->det));
     }
   }
   return hipSuccess;
@@ -1543,10 +1737,10 @@ hipError_t trainer_step(Trainer* t, float* params, float* grads, const float* vi
     // record columns: dgi 192 | dgh 192 | hprev 64 | u 2 | da1 32 | h 64 | do 4 | relu(a1) 32
     const float *dgi = fb, *dgh = fb + 192, *hprev = fb + 384, *u = fb + 448, *da1 = fb + 450, *hh = fb + 482,
                 *dout = fb + 546, *ra1 = fb + 550;
-    TRY(gemm(true, false, dgi, ld, u, ld, grads + t->f_wih, 2, 192, 2, R, 0, s));
-    TRY(gemm(true, false, dgh, ld, hprev, ld, grads + t->f_whh, 64, 192, 64, R, 0, s));
-    TRY(gemm(true, false, da1, ld, hh, ld, grads + t->f_w1, 64, 32, 64, R, 0, s));
-    TRY(gemm(true, false, dout, ld, ra1, ld, grads + t->f_w2, 32, 4, 32, R, 0, s));
+    TRY(gemm(true, false, dgi, ld, u, ld, grads + t->f_wih, 2, 192, 2, R, 0, s, t->det));
+    TRY(gemm(true, false, dgh, ld, hprev, ld, grads + t->f_whh, 64, 192, 64, R, 0, s, t->det));
+    TRY(gemm(true, false, da1, ld, hh, ld, grads + t->f_w1, 64, 32, 64, R, 0, s, t->det));
+    TRY(gemm(true, false, dout, ld, ra1, ld, grads + t->f_w2, 32, 4, 32, R, 0, s, t->det));
     ColsumSegs g;
     const float* cols[4] = {dgi, dgh, da1, dout};
     const int ns[4] = {192, 192, 32, 4};
@@ -1587,9 +1781,9 @@ hipError_t cil_trainer_step(Trainer* t, float* params, float* grads, const float
     const float* rb = t->flowbuf;  // [R][CIL_TRAIN_REC]: dgi 192 | dgh 192 | h_prev 64 | h 64 | x_in 2 | dout 2
     const int ld = CIL_TRAIN_REC;
     const float *dgi = rb, *dgh = rb + 192, *hprev = rb + 384, *hh = rb + 448, *xin = rb + 512, *dout = rb + 514;
-    TRY(gemm(true, false, dgi, ld, xin, ld, grads + t->f_wih, 2, 192, 2, R, 0, s));
-    TRY(gemm(true, false, dgh, ld, hprev, ld, grads + t->f_whh, 64, 192, 64, R, 0, s));
-    TRY(gemm(true, false, dout, ld, hh, ld, grads + t->c_wo, 64, 2, 64, R, 0, s));
+    TRY(gemm(true, false, dgi, ld, xin, ld, grads + t->f_wih, 2, 192, 2, R, 0, s, t->det));
+    TRY(gemm(true, false, dgh, ld, hprev, ld, grads + t->f_whh, 64, 192, 64, R, 0, s, t->det));
+    TRY(gemm(true, false, dout, ld, hh, ld, grads + t->c_wo, 64, 2, 64, R, 0, s, t->det));
     ColsumSegs g;
     const float* cols[3] = {dgi, dgh, dout};
     const int ns[3] = {192, 192, 2};

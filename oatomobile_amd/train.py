@@ -22,6 +22,11 @@ reduces, and the averaged gradient — not the local one — is what `clip=True`
 
 `CILTrainer` is the same machinery for `BehaviouralModel` (cil/train.py): the same encoder and merger halves, the GRU
 decoder's backward-through-time (`cil_train_kernel`) and the L1 loss in place of the flow; no target perturbation.
+
+By default a step's sums over the batch are added with float atomics in three kernels, so two runs differ in the last
+bits and drift apart over Adam steps.  `DIMTrainer(..., deterministic=True)` / `CILTrainer(..., deterministic=True)`
+replace them with partial tables added in a fixed order: the same bits on every run (see the class docstrings for
+what is and is not covered).
 """
 
 import ctypes
@@ -47,7 +52,7 @@ class _PackedTrainer:
   _state_dict_spec = None  # in_channels -> ordered [(key, shape)] of the model's state_dict
 
   def __init__(self, model, lr: float, weight_decay: float, max_batch: int, device: Optional[torch.device], betas,
-               eps: float, group) -> None:
+               eps: float, group, deterministic: bool = False) -> None:
     name = type(self).__name__
     if not torch.cuda.is_available():
       raise RuntimeError("oatomobile_amd.%s needs a ROCm device; there is no CPU path." % name)
@@ -71,6 +76,10 @@ class _PackedTrainer:
     self._lib = _lib.load()
     self._h = ctypes.c_void_p(0)
     n = self._create()
+    self._deterministic = False
+    if deterministic:  # allocates the partial-sum workspace (about 25 MB)
+      _lib.check(self._lib.rip_train_set_option(self._h, _lib.TRAIN_OPT_DETERMINISTIC, 1))
+      self._deterministic = True
     spec_n = sum(int(np.prod(s)) if len(s) else 1 for _, s in self._packed_spec())
     if n != spec_n:
       raise RuntimeError("packed layout mismatch: library %d, state_dict spec %d" % (n, spec_n))
@@ -90,6 +99,11 @@ class _PackedTrainer:
   def _create(self) -> int:
     """Creates `self._h`; returns the library's packed numel."""
     raise NotImplementedError
+
+  @property
+  def deterministic(self) -> bool:
+    """Was this trainer built with `deterministic=True` (the same bits on every run; see the class docstring)."""
+    return self._deterministic
 
   def _packed_spec(self):
     return [(k, s) for (k, s) in type(self)._state_dict_spec(self._C) if not k.endswith("num_batches_tracked")]
@@ -311,15 +325,24 @@ class _PackedTrainer:
 
 
 class DIMTrainer(_PackedTrainer):
-  """One model, one device; owns the packed parameter / gradient / Adam-moment tensors and the HIP workspace."""
+  """One model, one device; owns the packed parameter / gradient / Adam-moment tensors and the HIP workspace.
+
+  `deterministic=True` switches the deterministic mode on (`rip_train_set_option`): `backward`,
+  `train_step`, `evaluate_step`, `train_epoch` and `evaluate_epoch` then produce the same bits on every run, in every
+  trainer and every process, for the same inputs, the same state (parameters, Adam moments, step count), the same batch
+  size, an identically seeded `generator` and the same device model.  This holds at world size 1 or with `group=None`;
+  with a `group` the all-reduce's order belongs to the backend and is not covered.  Nothing is promised across batch
+  sizes, world sizes or device models, and the mode's results equal the default's to fp32 rounding, not bit for bit.
+  The target noise and the dropout mask of `train_step` come from torch's default device generator unless passed in
+  (`y=`, `dropout_mask=`): seed it, or pass them, to repeat a single step."""
 
   _state_dict_spec = staticmethod(arch.state_dict_spec)
 
   def __init__(self, model: ImitativeModel, lr: float = 1e-3, weight_decay: float = 0.0, noise_level: float = 1e-2,
                max_batch: int = 512, device: Optional[torch.device] = None, betas=(0.9, 0.999), eps: float = 1e-8,
-               group=None) -> None:
+               group=None, deterministic: bool = False) -> None:
     self._noise = float(noise_level)
-    super().__init__(model, lr, weight_decay, max_batch, device, betas, eps, group)
+    super().__init__(model, lr, weight_decay, max_batch, device, betas, eps, group, deterministic)
 
   def _create(self) -> int:
     _lib.check(self._lib.rip_train_create(ctypes.byref(self._h), self._C, self._max_batch, self._device.index))
@@ -394,14 +417,22 @@ class CILTrainer(_PackedTrainer):
   `player_future [B,T,>=2]`, T = `model._output_shape[0]` (the reference trains with T = 4).  Loss:
   `mean_b sum_{t,d} |predictions - player_future[..., :2]|` (nn.L1Loss(reduction="none") summed over [-2, -1]).
   Train mode: BatchNorm batch statistics (running statistics updated), Dropout(0.2) before the classifier — the only
-  random draw (there is no target perturbation); `dropout_mask=` replays one."""
+  random draw (there is no target perturbation); `dropout_mask=` replays one.
+
+  `deterministic=True` switches the deterministic mode on (`rip_train_set_option`): `backward`,
+  `train_step`, `evaluate_step`, `train_epoch` and `evaluate_epoch` then produce the same bits on every run, in every
+  trainer and every process, for the same inputs, the same state (parameters, Adam moments, step count), the same batch
+  size, an identically seeded `generator` and the same device model.  This holds at world size 1 or with `group=None`;
+  with a `group` the all-reduce's order belongs to the backend and is not covered.  Nothing is promised across batch
+  sizes, world sizes or device models, and the mode's results equal the default's to fp32 rounding, not bit for bit."""
 
   _state_dict_spec = staticmethod(arch.cil_state_dict_spec)
 
   def __init__(self, model: BehaviouralModel, lr: float = 1e-3, weight_decay: float = 0.0, max_batch: int = 512,
-               device: Optional[torch.device] = None, betas=(0.9, 0.999), eps: float = 1e-8, group=None) -> None:
+               device: Optional[torch.device] = None, betas=(0.9, 0.999), eps: float = 1e-8, group=None,
+               deterministic: bool = False) -> None:
     self._T = int(model._output_shape[0])
-    super().__init__(model, lr, weight_decay, max_batch, device, betas, eps, group)
+    super().__init__(model, lr, weight_decay, max_batch, device, betas, eps, group, deterministic)
     self.predictions = None
 
   _epoch_mode = True

@@ -66,6 +66,7 @@ enum { RIP_ENC_FP32 = 0, RIP_ENC_BF16 = 1 };
 #define RIP_HIDDEN 64
 #define RIP_MAX_MODELS 8
 #define RIP_MAX_STEPS 64
+#define RIP_MAX_GOALS 64 /* goal waypoints per observation (the reference's observation spec has up to 20) */
 
 /* ABI version of this header (bumped on any signature change). */
 int rip_abi_version(void);
@@ -126,7 +127,9 @@ int rip_encode_tap(rip_handle* h, const float* visual_dev, int B, int k, int enc
 
 /* Fused R2+R3+R4 for the agent's hot loop: raw sensor BEV [B,H,W,C]
  * (channels_last=1) or [B,C,H,W] -> z (any H, W >= 1 like F.interpolate; the
- * CARLA sensor gives 200 x 200).  Same results as rip_transform + rip_encode. */
+ * CARLA sensor gives 200 x 200: up to 208 x 208 runs the LDS-tiled transform, larger
+ * or 4-channel inputs a thread-per-output one).  Same results as rip_transform +
+ * rip_encode. */
 int rip_encode_raw(rip_handle* h, const float* lidar_dev, int channels_last, int H, int W, const float* vec_dev,
                    int B, int k_begin, int k_count, int enc_dtype, float* z_dev, rip_stream_t stream);
 
@@ -183,7 +186,10 @@ int rip_goal_likelihood_vjp(const float* y_dev, const float* goal_dev, int N, in
  * S[k,b,n] = log_prob_k - logabsdet_k (+ goal log-likelihood if goal_dev != NULL)
  * for models [k_begin, k_begin+k_count).  z_dev [k_count,B,64]; y_dev [B,N,4,2];
  * goal_dev [B,G,2] or NULL; S_dev [k_count,B,N].  This [K,N] matrix is what the
- * multi-GPU all-gather carries. */
+ * multi-GPU all-gather carries.  With a goal 1 <= G <= RIP_MAX_GOALS, like every
+ * entry point that takes a handle and a goal (rip_search, rip_act, rip_act_stats,
+ * rip_dim_forward, rip_mp_update, rip_predict): RIP_EINVAL beyond it, nothing is
+ * launched.  The stateless rip_goal_likelihood / _vjp take any G >= 1. */
 int rip_score(rip_handle* h, int k_begin, int k_count, const float* z_dev, const float* y_dev,
               const float* goal_dev, int B, int N, int G, float epsilon, float* S_dev, rip_stream_t stream);
 

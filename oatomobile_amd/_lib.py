@@ -201,6 +201,7 @@ class Handle:
     check(self._lib.rip_create(ctypes.byref(self._h), num_models, in_channels, max_batch, max_candidates, device_index))
     self.num_models, self.in_channels, self.max_batch, self.device_index = num_models, in_channels, max_batch, device_index
     self.max_candidates = max_candidates
+    self.options = {}  # option -> the value last set through `set_option` (what a second handle over the same models mirrors)
 
   def stream(self) -> c_void_p:
     """torch's current stream on THIS handle's device."""
@@ -217,6 +218,7 @@ class Handle:
 
   def set_option(self, option: int, value: int) -> None:
     check(self._lib.rip_set_option(self._h, option, value))
+    self.options[option] = value
 
   def kernel_log(self) -> list:
     """The encoder kernels the handle's last encode / tap call launched (after `set_option(OPT_KERNEL_LOG, 1)`), one

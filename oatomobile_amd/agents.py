@@ -238,6 +238,7 @@ class RIPAgent(SetPointAgent):
     self._eager_pending = False  # plan_batch* work launched on torch's current stream since the last __call__
     self._use_graph = bool(graph) and os.environ.get("RIP_NO_GRAPH", "0") != "1"
     self._online = {}  # (H, W, G) -> captured one-observation pipeline
+    self._replay_twin = None  # `replay_twin()`: the second handle of `replay.replay_cache(streams=2)`
 
   def _sync_weights(self) -> bool:
     """Uploads the weights of every model whose version changed since the last upload."""
@@ -257,10 +258,25 @@ class RIPAgent(SetPointAgent):
     other._x0_rows = self._x0_rows
     return other
 
+  def replay_twin(self) -> "RIPAgent":
+    """The cached `twin()` of `replay.replay_cache(streams=2)`, brought up to date: the options set on this agent's handle
+    since it was built (`Handle.set_option`: kernel selection, encoder variant) are set on the twin's handle as well, so
+    that both lanes launch the same kernels.  `refresh()` re-uploads the twin's weights with this agent's."""
+    if self._replay_twin is None:
+      self._replay_twin = self.twin()
+    theirs = self._replay_twin._handle
+    for option, value in self._handle.options.items():
+      if option != _lib.OPT_DEBUG_ENCODER_FAULT and theirs.options.get(option) != value:  # (a one-shot test hook, no setting)
+        theirs.set_option(option, value)
+    return self._replay_twin
+
   def refresh(self) -> None:
-    """Force a re-upload of all model weights (after in-place parameter edits without `model.refresh()`)."""
+    """Force a re-upload of all model weights (after in-place parameter edits without `model.refresh()`), the cached
+    replay twin's snapshot included."""
     self._versions = [None] * len(self._models)
     self._sync_weights()
+    if self._replay_twin is not None:
+      self._replay_twin.refresh()
 
   def _x0(self, batch: int) -> torch.Tensor:
     if batch not in self._x0_cache:
@@ -327,7 +343,8 @@ class RIPAgent(SetPointAgent):
                  return_loss: bool = False, interpolate: bool = False, out: Optional[torch.Tensor] = None,
                  return_stats: bool = False):
     """Device-resident batched planning: lidar [B,H,W,C] (sensor layout; 200 x 200 from CARLA), vec [B,5],
-    goal [B,G,2] -> plans [B,4,2] (and best losses [B,N]).  One rip_act call (transform + K encoders + search).
+    goal [B,G,2] with 1 <= G <= 64 (RIP_MAX_GOALS; `_lib.RipError` beyond it, nothing is launched) -> plans [B,4,2]
+    (and best losses [B,N]).  One rip_act call (transform + K encoders + search).
     `interpolate=True` returns what `__call__` returns per observation instead — the [B,30,3] float64 plans of
     rip/agent.py:141-151 — computed by the candidate-selection kernel (R11 on the device, bit-identical to the
     reference's scipy arithmetic); `out` = a caller-owned result tensor to write into.  `return_stats=True` appends

@@ -205,6 +205,19 @@ void launch_transform_tiled(const TIN* in, const float* lut, int B, int H, int W
   hipLaunchKernelGGL((transform_kernel<C, CL, TIN>), dim3(tiles, tiles, B), dim3(256), lds, s, in, lut, H, W, O, out);
 }
 
+// The blend of the four neighbours with every rounding spelled out, in the order the compiler gives the tiled kernels'
+// expression `hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11)` under fp-contract=fast (one product of each row
+// rounded, the other fused into it; the two row products rounded, then added).  Left to the compiler, the generic kernel
+// fused the other product of a row: its outputs sat one ulp from the tiled kernels' on about one output in a thousand,
+// and rip_gather_batch_u8 with C = 4 (tiled) was not "rip_transform(lut[codes[rows]]) bit for bit" (generic for C = 4)
+// as include/rip_hip.h has it — found by tests/test_shapes.py.
+__device__ __forceinline__ float bilerp_blend_as_tiled(float hy, float hx, float ly, float lx, float v00, float v01,
+                                                       float v10, float v11) {
+  const float top = fmaf(lx, v01, __fmul_rn(hx, v00));
+  const float bot = fmaf(hx, v10, __fmul_rn(lx, v11));
+  return __fadd_rn(__fmul_rn(hy, top), __fmul_rn(ly, bot));
+}
+
 // generic fallback (any scale): one thread per output element
 __global__ void transform_generic_kernel(const float* __restrict__ in, int B, int C, int H, int W, int channels_last,
                                          int O, float* __restrict__ out) {
@@ -222,7 +235,7 @@ __global__ void transform_generic_kernel(const float* __restrict__ in, int B, in
     const float v01 = bilerp_fetch(in, b, c, y0, x1, C, H, W, channels_last);
     const float v10 = bilerp_fetch(in, b, c, y1, x0, C, H, W, channels_last);
     const float v11 = bilerp_fetch(in, b, c, y1, x1, C, H, W, channels_last);
-    out[idx] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+    out[idx] = bilerp_blend_as_tiled(hy, hx, ly, lx, v00, v01, v10, v11);
   }
 }
 

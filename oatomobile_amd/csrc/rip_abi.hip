@@ -21,6 +21,7 @@
 using namespace rip;
 
 static_assert(RIP_MAX_MODELS == rip::MAX_MODELS, "header / kernel constant mismatch");
+static_assert(RIP_MAX_GOALS == rip::MAX_GOALS, "header / kernel constant mismatch");
 static_assert(RIP_ALGO_WCM == rip::ALGO_WCM && RIP_ALGO_MA == rip::ALGO_MA && RIP_ALGO_BCM == rip::ALGO_BCM, "algo ids");
 
 struct rip_handle {
@@ -712,7 +713,8 @@ int rip_score(rip_handle* h, int k_begin, int k_count, const float* z_dev, const
   if (rc != RIP_OK) return rc;
   REQUIRE(z_dev != nullptr && y_dev != nullptr && S_dev != nullptr, "NULL argument");
   REQUIRE(B >= 1 && N >= 1, "bad shape B=%d N=%d", B, N);
-  REQUIRE(goal_dev == nullptr || (G >= 1 && epsilon > 0.f), "bad goal arguments G=%d eps=%g", G, epsilon);
+  REQUIRE(goal_dev == nullptr || (G >= 1 && G <= rip::MAX_GOALS && epsilon > 0.f), "bad goal arguments G=%d (1..%d) eps=%g", G,
+          rip::MAX_GOALS, epsilon);
   ENTER(h, stream);
   HIP_TRY(launch_score(h->flow_w, k_begin, k_count, z_dev, y_dev, goal_dev, B, N, G, epsilon, S_dev, (hipStream_t)stream));
   return RIP_OK;
@@ -950,6 +952,8 @@ int rip_act(rip_handle* h, const float* lidar_dev, int channels_last, int H, int
             rip_stream_t stream) {
   REQUIRE(h != nullptr, "handle is NULL");
   REQUIRE(plan_dev != nullptr || plan_interp_dev != nullptr, "plan_dev and plan_interp_dev are both NULL");
+  // (before the encoder is launched: a goal count the search refuses must not leave half a call on the stream)
+  REQUIRE(goal_dev == nullptr || (G >= 1 && G <= rip::MAX_GOALS), "G=%d must be in [1,%d] with a goal", G, rip::MAX_GOALS);
   int rc = rip_encode_raw(h, lidar_dev, channels_last, H, W, vec_dev, B, 0, h->K, enc_dtype, h->z, stream);
   if (rc != RIP_OK) return rc;
   // h->z is [K][B][64] because rip_encode packs by the B it was given
@@ -984,6 +988,8 @@ int rip_act_stats(rip_handle* h, const float* lidar_dev, int channels_last, int 
                    enc_dtype, plan_dev, loss_best_dev, plan_interp_dev, stream);
   REQUIRE(h != nullptr, "handle is NULL");
   REQUIRE(plan_dev != nullptr || plan_interp_dev != nullptr, "plan_dev and plan_interp_dev are both NULL");
+  // (before the encoder is launched: a goal count the search refuses must not leave half a call on the stream)
+  REQUIRE(goal_dev == nullptr || (G >= 1 && G <= rip::MAX_GOALS), "G=%d must be in [1,%d] with a goal", G, rip::MAX_GOALS);
   int rc = rip_encode_raw(h, lidar_dev, channels_last, H, W, vec_dev, B, 0, h->K, enc_dtype, h->z, stream);  // B <= max_batch
   if (rc != RIP_OK) return rc;
   float* plan = plan_dev != nullptr ? plan_dev : h->stat_plan;

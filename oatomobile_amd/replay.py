@@ -629,9 +629,7 @@ def replay_cache(agent, cache: "PackedCache", batch_size: int, interpolate: bool
   copy = torch.cuda.Stream(device=dev)
   main = torch.cuda.current_stream(dev)
   if streams == 2:
-    if getattr(agent, "_replay_twin", None) is None:
-      agent._replay_twin = agent.twin()
-    agents = [agent, agent._replay_twin]
+    agents = [agent, agent.replay_twin()]  # (weights and handle options follow the agent's: RIPAgent.replay_twin)
     lanes = [torch.cuda.Stream(device=dev) for _ in range(2)]
     for s in lanes:
       s.wait_stream(main)

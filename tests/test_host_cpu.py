@@ -485,3 +485,24 @@ def test_bench_dump_outputs_writes_npy_and_samples_past_the_cap(tmp_path, monkey
   np.testing.assert_array_equal(s0, a[rows])
   with pytest.raises(AssertionError):
     bench._dump_outputs(str(tmp_path / "ints"), plans=np.zeros((2, 3), np.int32))
+
+
+def test_bilinear_swap_reference_is_the_oracles_transform():
+  """tests/helpers.py:bilinear_swap_ref — the float64 blend over the reference's own fp32 source coordinates that
+  tests/test_shapes.py holds the transform kernels against — is pinned to the oracle's `transform_visual`
+  (F.interpolate, align_corners=True, then the H/W swap) on every BEV size and output size those tests run, dense inputs
+  in [0, 1).  atol 2e-6, the suite's transform tolerance: the blend is four fp32 roundings of values <= 1 on torch's side
+  (measured: 1.2e-7 at most; float64 COORDINATES would sit up to 2e-5 away, which is why the coordinates are fp32)."""
+  from oracle import reference_cpu as O
+  from tests.helpers import TRANSFORM_CASES, bilinear_swap_ref
+  worst = 0.0
+  for n, (H, W, out) in enumerate(TRANSFORM_CASES):
+    x = np.random.default_rng(9000 + n).random((2, 3, H, W)).astype(np.float32)
+    want = O.transform_visual(torch.from_numpy(x), (out, out)).numpy()
+    got = bilinear_swap_ref(x, out)
+    assert got.shape == want.shape == (2, 3, out, out) and got.dtype == np.float64
+    worst = max(worst, float(np.abs(got - want).max()))
+    np.testing.assert_allclose(got, want, rtol=0, atol=2e-6, err_msg="H=%d W=%d out=%d" % (H, W, out))
+  print("bilinear_swap_ref against the oracle's transform_visual: max|d| = %.3g over %d shapes" % (worst, len(TRANSFORM_CASES)))
+  x = np.random.default_rng(1).random((1, 2, 100, 100)).astype(np.float32)
+  np.testing.assert_array_equal(bilinear_swap_ref(x, 100), x.transpose(0, 1, 3, 2).astype(np.float64))  # scale 1: a transpose

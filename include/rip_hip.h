@@ -28,7 +28,8 @@
  *     makes that device current for the duration of the call and restores the
  *     caller's current device before returning.  The stateless entry points
  *     (rip_transform, rip_goal_likelihood, rip_goal_likelihood_vjp,
- *     rip_lidar_bev, rip_cil_decode, rip_gather_batch_u8, rip_sample_normal) launch
+ *     rip_lidar_bev, rip_cil_decode, rip_gather_batch_u8, rip_sample_normal,
+ *     rip_hindsight_targets, rip_code_bev_u8) launch
  *     on the caller's current device, which must own the pointers.
  *   - a handle's scratch is shared by its calls, so a handle is single-stream
  *     and not thread-safe: when consecutive calls on one handle name different
@@ -245,6 +246,34 @@ int rip_mp_update(rip_handle* h, int k_fwd, const float* z_fwd_dev, const float*
  * bev_dev [B,200,200,2] fp32: per height channel (z <= -2.5 / z >= -2.5) the np.histogramdd counts over
  * np.linspace(-50, 51, 201)^2, clipped at 5 and divided by 5.  Bit-exact with the reference.  Stateless. */
 int rip_lidar_bev(const float* points_dev, const int32_t* offsets_dev, int B, float* bev_dev, rip_stream_t stream);
+
+/* Hindsight labelling of a recording — CARLADataset.process (oatomobile/datasets/carla.py:237-325) for all requested
+ * frames in one launch.  location_dev [N,3] fp32, rotation_dev [N,3] fp32 (pitch, yaw, roll in degrees, carla.Rotation's
+ * order), episode_dev [N] int32 (the episode each frame belongs to), frames_dev [M] int32: window m is frame
+ * i = frames[m] with its P predecessors and L successors.  Outputs, each optional (NULL skips it):
+ *   future64_dev [M,L,3], past64_dev [M,P,3]  fp64: world2local (utils/carla.py:642-674) of frames i+1..i+L and
+ *     i-P..i-1 about frame i: the difference of the fp32 locations in fp32, the rotation matrix ('sxyz'
+ *     euler2mat(roll, pitch, yaw) transposed, from deg2rad of the angles) and the 3x3 product in fp64;
+ *   future_xy_dev [M,L,2] fp32 = future64[..., :2];
+ *   goal_dev [M,G,2] fp32 = future64[goal_stride-1::goal_stride][:G, :2], the last waypoint repeated up to G (needs
+ *     L >= goal_stride);
+ *   mode_dev [M] fp32: the driving-mode label of load_datum (datasets/carla.py:148-162) from the fp32 last waypoint;
+ *   valid_dev [M] uint8.
+ * A window is valid when i - P >= 0, i + L < N and episode[i - P] == episode[i] == episode[i + L]; an invalid one reads
+ * nothing out of range, writes NaN rows and valid = 0.  L >= 1, P >= 0, 1 <= G <= RIP_MAX_GOALS, goal_stride >= 1.
+ * Stateless: launches on the caller's current device. */
+int rip_hindsight_targets(const float* location_dev, const float* rotation_dev, const int32_t* episode_dev, int N,
+                          const int32_t* frames_dev, int M, int L, int P, int G, int goal_stride, double* future64_dev,
+                          double* past64_dev, float* future_xy_dev, float* goal_dev, float* mode_dev, uint8_t* valid_dev,
+                          rip_stream_t stream);
+
+/* The uint8 coding of the packed replay cache against a FIXED table: bev_dev [B,H,W,C] fp32 is read as uint32 bit
+ * patterns (-0.0 and +0.0 are different values), table_dev = the first n_values (1..256) entries of a cache's lut.npy as
+ * uint32, ascending; codes_dev [B,H,W,C] uint8 receives the index of every cell's pattern.  A cell whose pattern is not
+ * in the table — every NaN among them — is coded 0 and counted into *miss_dev (uint32, device memory; the caller zeroes
+ * it and reads it when it synchronises anyway).  Stateless: launches on the caller's current device. */
+int rip_code_bev_u8(const float* bev_dev, int B, int H, int W, int C, const uint32_t* table_dev, int n_values,
+                    uint8_t* codes_dev, uint32_t* miss_dev, rip_stream_t stream);
 
 /* N4 — BehaviouralModel.forward after the encoder (oatomobile/baselines/torch/cil/model.py:88-127):
  * merger MLP over cat(features, velocity, is_at_traffic_light, traffic_light_state, mode), then the GRUCell + Linear

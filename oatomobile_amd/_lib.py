@@ -102,6 +102,11 @@ SIGNATURES = [
         c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p
     ]),
+    ("rip_hindsight_targets", c_int, [
+        c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+        c_void_p, c_void_p, c_void_p, c_void_p
+    ]),
+    ("rip_code_bev_u8", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 ]
 ABI_VERSION = 4
 

@@ -2,7 +2,7 @@
 (oatomobile/baselines/torch/dim/train.py:85-322, cil/train.py:84-287) on this package's pieces.
 
     datum files (<dataset_dir>/{train,val}/*.npz) -> replay.pack_cache(targets=True) under --cache_dir (reused while
-    its sources.json matches the datum files) -> replay.DeviceCache -> DIMTrainer / CILTrainer.train_epoch (batches assembled on the GPU) and
+    its sources.json matches the datum files; with --raw_dataset: raw episodes -> replay.pack_episodes) -> replay.DeviceCache -> DIMTrainer / CILTrainer.train_epoch (batches assembled on the GPU) and
     evaluate_epoch at 5x the batch -> <output_dir>/ckpts/model-{epoch}.pt every --save_model_frequency epochs
     (Checkpointer.save: torch.save(model.state_dict())) and <output_dir>/logs/metrics.jsonl.
 
@@ -39,6 +39,10 @@ def parse_args(kind: str, argv=None) -> argparse.Namespace:
                  help="If True it clips the gradients norm to 1.0.")
   p.add_argument("--cache_dir", default=None, help="Packed caches of train/ and val/ (default <output_dir>/cache); "
                  "reused while they match the datum files.")
+  p.add_argument("--raw_dataset", action="store_true", default=False,
+                 help="<dataset_dir>/{train,val} hold RAW episodes (<episode>/<sample>.npz + metadata), not processed "
+                 "datums: they are labelled in hindsight and packed in one step (replay.pack_episodes, the defaults of "
+                 "CARLADataset.process: future 80, past 20, every 5th frame).")
   p.add_argument("--seed", type=int, default=0, help="Seeds the initial weights and the epoch generator.")
   p.add_argument("--deterministic", action="store_true", default=False,
                  help="Fixed-order sums in the training step: the same --seed, data, batch size and device model give "
@@ -64,20 +68,26 @@ def _sources(files):
   return out
 
 
-def packed(split_dir: str, cache_dir: str):
+def packed(split_dir: str, cache_dir: str, raw: bool = False, device=None):
   """The packed cache of the datums in `split_dir`, packed once into `cache_dir`.  It is reused only when it has the
   training targets and `sources.json` lists the same datum files (name, size, modification time); a changed, added or
-  removed file repacks it."""
+  removed file repacks it.  `raw`: `split_dir` holds raw episodes, packed with `replay.pack_episodes` (labelled on
+  `device`, None = numpy); `sources.json` then lists the raw sample files of every episode."""
   from oatomobile_amd import replay
-  files = sorted(glob.glob(os.path.join(split_dir, "*.npz")))  # replay.as_torch's order
-  if not files:
-    raise SystemExit("no datum files (*.npz) under %s" % split_dir)
+  if raw:
+    files = sorted(glob.glob(os.path.join(split_dir, "*", "*.npz")))
+    if not files:
+      raise SystemExit("no raw episodes (<episode>/*.npz) under %s" % split_dir)
+  else:
+    files = sorted(glob.glob(os.path.join(split_dir, "*.npz")))  # replay.as_torch's order
+    if not files:
+      raise SystemExit("no datum files (*.npz) under %s" % split_dir)
   sources = _sources(files)
   try:
     with open(os.path.join(cache_dir, SOURCES)) as f:
       recorded = json.load(f)
     cache = replay.PackedCache(cache_dir)
-    if cache.has_targets and len(cache) == len(files) and recorded == sources:
+    if cache.has_targets and (raw or len(cache) == len(files)) and recorded == sources:
       return cache
   except (OSError, ValueError):
     pass
@@ -85,7 +95,7 @@ def packed(split_dir: str, cache_dir: str):
     os.remove(os.path.join(cache_dir, SOURCES))
   except OSError:
     pass
-  cache = replay.pack_cache(files, cache_dir, targets=True)
+  cache = replay.pack_episodes(split_dir, cache_dir, device=device) if raw else replay.pack_cache(files, cache_dir, targets=True)
   with open(os.path.join(cache_dir, SOURCES), "w") as f:
     json.dump(sources, f)
   return cache
@@ -112,7 +122,8 @@ def main(kind: str, argv=None) -> int:
   for d in (args.output_dir, log_dir, ckpt_dir):
     os.makedirs(d, exist_ok=True)
   cache_dir = args.cache_dir or os.path.join(args.output_dir, "cache")
-  caches = {split: packed(os.path.join(args.dataset_dir, split), os.path.join(cache_dir, split)) for split in ("train", "val")}
+  caches = {split: packed(os.path.join(args.dataset_dir, split), os.path.join(cache_dir, split), args.raw_dataset,
+                          device if args.raw_dataset else None) for split in ("train", "val")}
   C = caches["train"].channels
   data = {split: replay.DeviceCache(c, device) for split, c in caches.items()}
   T = args.num_timesteps_to_keep

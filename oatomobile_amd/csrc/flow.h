@@ -135,6 +135,14 @@ hipError_t launch_dim_select(const float* flow_w_k, const float* z, const float*
 hipError_t launch_cil_decode(const float* feat, const float* vec, const float* w, int B, int T, float* y, hipStream_t s);  // cil.hip
 int cil_blob_floats();
 hipError_t launch_lidar_bev(const float* points, const int* offsets, int B, float* bev, hipStream_t s);  // lidar.hip
+// lidar.hip: hindsight labels of the windows `frames` of a pose track (any output may be null), and the uint8 coding of a
+// float32 BEV against a fixed table of bit patterns with a device miss counter
+hipError_t launch_hindsight_targets(const float* location, const float* rotation, const int* episode, int N,
+                                    const int* frames, int M, int L, int P, int G, int goal_stride, double* future64,
+                                    double* past64, float* future_xy, float* goal, float* mode, unsigned char* valid,
+                                    hipStream_t s);
+hipError_t launch_code_bev_u8(const float* bev, long long cells, const unsigned* table, int n_values, unsigned char* codes,
+                              unsigned* miss, hipStream_t s);
 hipError_t launch_aggregate_scores(const float* S, int K, int B, int N, int algorithm, float* loss, int32_t* best,
                                    hipStream_t s);
 size_t search_lds_bytes(int K);

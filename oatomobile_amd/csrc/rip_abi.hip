@@ -736,6 +736,35 @@ int rip_lidar_bev(const float* points_dev, const int32_t* offsets_dev, int B, fl
   return RIP_OK;
 }
 
+int rip_hindsight_targets(const float* location_dev, const float* rotation_dev, const int32_t* episode_dev, int N,
+                          const int32_t* frames_dev, int M, int L, int P, int G, int goal_stride, double* future64_dev,
+                          double* past64_dev, float* future_xy_dev, float* goal_dev, float* mode_dev, uint8_t* valid_dev,
+                          rip_stream_t stream) {
+  REQUIRE(N >= 0 && M >= 0, "bad shape N=%d M=%d", N, M);
+  REQUIRE(L >= 1, "future length L=%d below 1", L);
+  REQUIRE(P >= 0, "past length P=%d below 0", P);
+  REQUIRE(G >= 1 && G <= RIP_MAX_GOALS, "G=%d outside [1, %d]", G, RIP_MAX_GOALS);
+  REQUIRE(goal_stride >= 1, "goal_stride=%d below 1", goal_stride);
+  REQUIRE(goal_dev == nullptr || L >= goal_stride, "a future of L=%d steps has no waypoint at goal_stride=%d", L, goal_stride);
+  REQUIRE(M == 0 || frames_dev != nullptr, "frames_dev is NULL");
+  REQUIRE(M == 0 || N == 0 || (location_dev != nullptr && rotation_dev != nullptr && episode_dev != nullptr),
+          "location_dev / rotation_dev / episode_dev is NULL");
+  HIP_TRY(launch_hindsight_targets(location_dev, rotation_dev, episode_dev, N, frames_dev, M, L, P, G, goal_stride,
+                                   future64_dev, past64_dev, future_xy_dev, goal_dev, mode_dev, valid_dev,
+                                   (hipStream_t)stream));
+  return RIP_OK;
+}
+
+int rip_code_bev_u8(const float* bev_dev, int B, int H, int W, int C, const uint32_t* table_dev, int n_values,
+                    uint8_t* codes_dev, uint32_t* miss_dev, rip_stream_t stream) {
+  REQUIRE(B >= 0 && H >= 1 && W >= 1 && C >= 1, "bad shape B=%d H=%d W=%d C=%d", B, H, W, C);
+  REQUIRE(n_values >= 1 && n_values <= 256, "n_values=%d outside [1, 256]", n_values);
+  REQUIRE(table_dev != nullptr && miss_dev != nullptr, "table_dev / miss_dev is NULL");
+  REQUIRE(B == 0 || (bev_dev != nullptr && codes_dev != nullptr), "bev_dev / codes_dev is NULL");
+  HIP_TRY(launch_code_bev_u8(bev_dev, (long long)B * H * W * C, table_dev, n_values, codes_dev, miss_dev, (hipStream_t)stream));
+  return RIP_OK;
+}
+
 int rip_cil_decode(const float* feat_dev, const float* vec_dev, const float* weights_dev, int B, int T, float* y_dev,
                    rip_stream_t stream) {
   REQUIRE(B >= 0 && T >= 1, "bad shape B=%d T=%d", B, T);

@@ -398,6 +398,13 @@ def pack_cache(files: Sequence[str], out_dir: str, num_goals: int = 10, goal_str
               off += int(size)
       if failure is not None:
         raise failure
+  return _write_cache(out_dir, spans, vec, goal, future if targets else None, mode if targets else None)
+
+
+def _write_cache(out_dir: str, spans, vec, goal, future, mode) -> "PackedCache":
+  """The end of a pack: unifies the value tables of `spans` [(row0, rows, table)], re-codes the rows of `codes.npy`
+  that were coded against another table than the final one, and writes lut / vec / goal (/ future / mode) beside it."""
+  targets = future is not None
   values = np.empty((0,), np.uint32)
   for _, _, t in spans:
     values = np.union1d(values, t).astype(np.uint32)
@@ -484,6 +491,135 @@ class PackedCache:
         yield c[:m], v[:m], g[:m]
 
 
+def _episodes(dataset_dir: str):
+  """The episodes of a raw dataset in sorted order: every sub-directory with a `metadata` file
+  (datasets/carla.py:260-268 skips the others) -> [(token, Episode, sample tokens in order)]."""
+  out = []
+  for token in sorted(os.listdir(dataset_dir)):
+    if os.path.isfile(os.path.join(dataset_dir, token, "metadata")):
+      episode = Episode(dataset_dir, token)
+      out.append((token, episode, episode.fetch()))
+  return out
+
+
+def _cuda_device(device, what: str) -> torch.device:
+  dev = torch.device(device)
+  if dev.type != "cuda":
+    raise RuntimeError("%s: device must be None (numpy) or a ROCm device, got %s" % (what, dev))
+  return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _hindsight_launch(location, rotation, episode, frames, L, P, G, goal_stride, want):
+  """One `rip_hindsight_targets` launch over device tensors -> dict of the outputs named in `want` (the others are
+  passed as NULL).  No synchronisation."""
+  from oatomobile_amd import _lib
+  dev, M = location.device, int(frames.numel())
+  spec = dict(future64=((M, L, 3), torch.float64), past64=((M, P, 3), torch.float64), future_xy=((M, L, 2), torch.float32),
+              goal=((M, G, 2), torch.float32), mode=((M,), torch.float32), valid=((M,), torch.uint8))
+  out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in spec.items() if k in want}
+  arg = lambda k: _lib.ptr(out[k], spec[k][1]) if k in out else _lib.ptr(None)
+  with torch.cuda.device(dev):  # stateless entry point: launches on the current device
+    _lib.check(_lib.load().rip_hindsight_targets(
+        _lib.ptr(location), _lib.ptr(rotation), _lib.ptr(episode, torch.int32), int(location.shape[0]),
+        _lib.ptr(frames, torch.int32), M, int(L), int(P), int(G), int(goal_stride), arg("future64"), arg("past64"),
+        arg("future_xy"), arg("goal"), arg("mode"), arg("valid"), _lib.current_stream(dev)))
+  return out
+
+
+def _episode_labels(name, episode, sequence, L, P, skips, device, want, G=1, goal_stride=1):
+  """The poses of an episode, read once per sample, and the hindsight labels of its windows
+  `range(P, len(sequence) - L, skips)` -> (frames, dict of host arrays): `_datum.hindsight_targets` for `device=None`,
+  else one `rip_hindsight_targets` launch.  `want` names the outputs (future64, past64, future_xy, goal, mode)."""
+  from oatomobile_amd import _datum
+  if len(sequence) < P + L + 1:  # datasets/carla.py:271 asserts here
+    raise ValueError("episode %s has %d samples, fewer than past_length + future_length + 1 = %d" %
+                     (name, len(sequence), P + L + 1))
+  location, rotation = [], []
+  for token in sequence:  # one open per sample; only the two small members are decompressed
+    with np.load(episode.sample_path(token), allow_pickle=True) as sample:
+      location.append(np.asarray(sample["location"]).reshape(3))
+      rotation.append(np.asarray(sample["rotation"]).reshape(3))
+  location, rotation = np.stack(location), np.stack(rotation)
+  frames = np.arange(P, len(sequence) - L, skips, dtype=np.int32)
+  if device is None:
+    future64, past64 = _datum.hindsight_targets(location, rotation, frames, L, P)
+    out = dict(future64=future64, past64=past64)
+    if {"future_xy", "goal", "mode"} & set(want):
+      out["future_xy"], out["goal"], out["mode"] = _datum.targets_from_future(future64, G, goal_stride)
+    return frames, {k: out[k] for k in want}
+  if location.dtype != np.float32 or rotation.dtype != np.float32:
+    raise ValueError("episode %s: the device path takes float32 poses (the sensors' dtype), got location %s, rotation %s; "
+                     "use device=None" % (name, location.dtype, rotation.dtype))
+  dev = _cuda_device(device, "hindsight labelling")
+  up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+  out = _hindsight_launch(up(location), up(rotation), torch.zeros(len(sequence), dtype=torch.int32, device=dev), up(frames),
+                          L, P, G, goal_stride, set(want) | {"valid"})
+  host = {k: v.cpu().numpy() for k, v in out.items()}
+  assert host.pop("valid").all()  # every window of range(P, n - L) is inside the episode
+  return frames, host
+
+
+def process(dataset_dir: str, output_dir: str, future_length: int = 80, past_length: int = 20, num_frame_skips: int = 5,
+            device=None) -> List[str]:
+  """`CARLADataset.process` (datasets/carla.py:237-325): raw episodes `<dataset_dir>/<episode>/<sample>.npz` ->
+  one datum `<output_dir>/<sample>.npz` per window `i in range(past_length, len(sequence) - future_length,
+  num_frame_skips)` of every episode (taken in sorted order): every key of the raw observation unchanged, plus
+  `player_future` [L,3] and `player_past` [P,3] (float64), the locations of the next L and previous P samples in the
+  sample's ego frame.  Returns the files written, in order.
+
+  Differences: the reference opens L + P + 1 compressed files per datum; here the pose of every sample is read once per
+  episode and the whole episode is labelled at once (`device=None`: numpy; a ROCm device: one `rip_hindsight_targets`
+  launch).  The reference swallows every exception per datum (no file, no message); here an episode shorter than
+  P + L + 1 samples is a ValueError that names it (the reference asserts) and any other error surfaces.  A directory
+  without a `metadata` file is skipped, like there."""
+  L, P, skips = int(future_length), int(past_length), int(num_frame_skips)
+  if L < 1 or P < 0 or skips < 1:
+    raise ValueError("process: future_length >= 1, past_length >= 0, num_frame_skips >= 1; got %d, %d, %d" % (L, P, skips))
+  os.makedirs(output_dir, exist_ok=True)
+  written = []
+  for name, episode, sequence in _episodes(dataset_dir):
+    frames, labels = _episode_labels(name, episode, sequence, L, P, skips, device, ("future64", "past64"))
+    for m, i in enumerate(frames):
+      observation = episode.read_sample(sequence[i])
+      path = os.path.join(output_dir, "%s.npz" % sequence[i])
+      np.savez_compressed(path, **observation, player_future=labels["future64"][m], player_past=labels["past64"][m])
+      written.append(path)
+  return written
+
+
+def pack_episodes(dataset_dir: str, out_dir: str, future_length: int = 80, past_length: int = 20, num_frame_skips: int = 5,
+                  num_goals: int = 10, goal_stride: int = 8, device=None, chunk: int = 256) -> "PackedCache":
+  """Raw episodes straight to a packed cache with training targets: `pack_cache(files of process(...), targets=True)`
+  without the datum files in between — rows in `process`'s order (episodes sorted, windows in sequence order), the same
+  six files.  `codes.npy`, `lut.npy`, `vec.npy` and `mode.npy` equal that cache's bit for bit; `future.npy` and
+  `goal.npy` equal it with `device=None` and are within one float32 ulp of it on a ROCm device (one
+  `rip_hindsight_targets` launch per episode).  Every raw sample is decompressed once: its pose when its episode is
+  labelled, its BEV only if it is a window's centre.  Packs in this process (`_datum.pack_span` with the labels handed
+  over, then the table unification of `pack_cache`)."""
+  from oatomobile_amd import _datum
+  L, P, skips, G = int(future_length), int(past_length), int(num_frame_skips), int(num_goals)
+  if L < 1 or P < 0 or skips < 1:
+    raise ValueError("pack_episodes: future_length >= 1, past_length >= 0, num_frame_skips >= 1; got %d, %d, %d" % (L, P, skips))
+  files, future, goal, mode = [], [], [], []
+  for name, episode, sequence in _episodes(dataset_dir):
+    frames, labels = _episode_labels(name, episode, sequence, L, P, skips, device, ("future_xy", "goal", "mode"), G,
+                                     int(goal_stride))
+    files += [episode.sample_path(sequence[i]) for i in frames]
+    future.append(labels["future_xy"])
+    goal.append(labels["goal"])
+    mode.append(labels["mode"])
+  if not files:
+    raise ValueError("pack_episodes: no episodes under %s" % dataset_dir)
+  os.makedirs(out_dir, exist_ok=True)
+  H, W, C = load_datum(files[0], modalities=("lidar",))["lidar"].shape
+  shape = (len(files), H, W, C)
+  codes = np.lib.format.open_memmap(os.path.join(out_dir, "codes.npy"), mode="w+", dtype=np.uint8, shape=shape)
+  del codes  # pack_span opens it itself
+  labels = (np.concatenate(future), np.concatenate(goal), np.concatenate(mode))
+  spans, vec, goal, future, mode = _datum.pack_span(files, 0, out_dir, shape, G, int(goal_stride), chunk, L, labels)
+  return _write_cache(out_dir, spans, vec, goal, future, mode)
+
+
 def downsample_stride(L: int, T: int) -> int:
   """transforms.downsample_target (torch/transforms.py:23-31) keeps `future[:, 0::L // T]`: that stride, or ValueError
   when the slice does not have exactly T steps (the reference would hand the model a target of another length)."""
@@ -555,6 +691,39 @@ class DeviceCache:
       self.mode = torch.from_numpy(np.array(cache.mode, np.float32)).to(dev)
       torch.cuda.synchronize(dev)  # the pinned slots are freed on return
 
+  @classmethod
+  def from_tensors(cls, codes, lut, vec, future, mode) -> "DeviceCache":
+    """A `DeviceCache` around device tensors that already exist (`DeviceRecorder.cache`): codes [n,H,W,C] uint8,
+    lut [256] float32, vec [n,5], future [n,L,2] and mode [n] float32, all contiguous and on one ROCm device.  Nothing is
+    copied."""
+    if not all(isinstance(t, torch.Tensor) for t in (codes, lut, vec, future, mode)):
+      raise TypeError("DeviceCache.from_tensors takes torch tensors")
+    if not codes.is_cuda:
+      raise RuntimeError("DeviceCache needs a ROCm device, got %s (no CPU path)" % codes.device)
+    for name, t, dt in (("codes", codes, torch.uint8), ("lut", lut, torch.float32), ("vec", vec, torch.float32),
+                        ("future", future, torch.float32), ("mode", mode, torch.float32)):
+      if t.dtype != dt:
+        raise ValueError("DeviceCache.from_tensors: %s must be %s, got %s" % (name, dt, t.dtype))
+      if t.device != codes.device:
+        raise RuntimeError("DeviceCache.from_tensors: %s is on %s, codes on %s" % (name, t.device, codes.device))
+      if not t.is_contiguous():
+        raise ValueError("DeviceCache.from_tensors: %s is not contiguous" % name)
+    if codes.dim() != 4:
+      raise ValueError("DeviceCache.from_tensors: codes must have shape [n,H,W,C], got %s" % (tuple(codes.shape),))
+    n, H, W, C = (int(v) for v in codes.shape)
+    from oatomobile_amd import _lib
+    _lib.expect_shape(lut, (256,), "lut")
+    _lib.expect_shape(vec, (n, 5), "vec")
+    _lib.expect_shape(future, (n, None, 2), "future")
+    _lib.expect_shape(mode, (n,), "mode")
+    if int(future.shape[1]) < 1:
+      raise ValueError("DeviceCache.from_tensors: future has no steps")
+    self = cls.__new__(cls)
+    self.device = codes.device
+    self.n, self.H, self.W, self.C, self.L = n, H, W, C, int(future.shape[1])
+    self.codes, self.lut, self.vec, self.future, self.mode = codes, lut, vec, future, mode
+    return self
+
   def __len__(self) -> int:
     return self.n
 
@@ -599,6 +768,123 @@ class DeviceCache:
     if mode:
       out["mode"] = mode_out
     return out
+
+
+class DeviceRecorder:
+  """Records driving on the device and labels it in hindsight: the way from what an agent just drove to a
+  `DeviceCache` the trainers take, without a file and without a host copy of the observations.
+
+      rec = DeviceRecorder.from_cache(train_cache, capacity=2000)     # the training set's table and BEV shape
+      rec.append(lidar=..., velocity=..., is_at_traffic_light=..., traffic_light_state=..., location=..., rotation=...)
+      rec.end_episode()                                               # windows do not cross this
+      data = rec.cache()                                              # DeviceCache of the frames with a full window
+
+  `append` takes host arrays or device tensors, codes the BEV against the fixed table with `rip_code_bev_u8` into row n
+  of a preallocated [capacity,H,W,C] uint8 tensor, stores vec and the pose beside it and does not synchronise; more
+  than `capacity` frames raise IndexError (from the host-side count).  `cache(num_frame_skips)` labels the frames
+  `range(P, len - L, skips)` of every episode with one `rip_hindsight_targets` launch, compacts their rows and returns
+  `DeviceCache.from_tensors(...)`; its one synchronisation reads the miss counter: a cell value that is not in the
+  table is a ValueError with the count (such a recording needs a cache packed from its own data).  `frames` holds the
+  labelled frame indices after `cache()`.  `lut` is a cache's `lut.npy` ([256] float32, NaN padded)."""
+
+  def __init__(self, capacity: int, shape, lut, device=None, future_length: int = 80, past_length: int = 20,
+               num_goals: int = 10, goal_stride: int = 8) -> None:
+    dev = _cuda_device("cuda" if device is None else device, "DeviceRecorder")
+    self.device, self.capacity = dev, int(capacity)
+    self.H, self.W, self.C = (int(v) for v in shape)
+    self.L, self.P, self.G, self.goal_stride = int(future_length), int(past_length), int(num_goals), int(goal_stride)
+    if self.capacity < 1 or min(self.H, self.W, self.C) < 1 or self.L < 1 or self.P < 0:
+      raise ValueError("DeviceRecorder: capacity, shape and future_length must be >= 1, past_length >= 0")
+    lut = np.ascontiguousarray(lut.detach().cpu().numpy() if isinstance(lut, torch.Tensor) else lut, dtype=np.float32)
+    if lut.shape != (256,):
+      raise ValueError("DeviceRecorder: lut must have shape [256], got %s" % (lut.shape,))
+    self.n_values = int((~np.isnan(lut)).sum())
+    bits = lut.view(np.uint32)[:self.n_values].astype(np.int64)
+    if self.n_values < 1 or np.isnan(lut[:self.n_values]).any() or (np.diff(bits) <= 0).any():
+      raise ValueError("DeviceRecorder: lut is not a cache's table (ascending bit patterns, then NaN padding)")
+    with torch.cuda.device(dev):
+      self.lut = torch.from_numpy(lut).to(dev)
+      self.codes = torch.empty((self.capacity, self.H, self.W, self.C), dtype=torch.uint8, device=dev)
+      self.vec = torch.empty((self.capacity, 5), device=dev)
+      self.location = torch.empty((self.capacity, 3), device=dev)
+      self.rotation = torch.empty((self.capacity, 3), device=dev)
+      self._miss = torch.zeros((1,), dtype=torch.int32, device=dev)  # a uint32 counter (rip_code_bev_u8)
+    self._n, self._episode, self._episodes = 0, 0, []
+    self.frames = None
+
+  @classmethod
+  def from_cache(cls, cache, capacity: int, device=None, **kwargs) -> "DeviceRecorder":
+    """A recorder with the table and BEV shape of an existing `PackedCache` or `DeviceCache` (record with the training
+    set's table); on the `DeviceCache`'s device unless `device` says otherwise."""
+    if isinstance(cache, DeviceCache):
+      return cls(capacity, (cache.H, cache.W, cache.C), cache.lut, cache.device if device is None else device, **kwargs)
+    return cls(capacity, cache.codes.shape[1:], cache.lut, device, **kwargs)
+
+  def __len__(self) -> int:
+    return self._n
+
+  def _f32(self, value, numel: int, what: str) -> torch.Tensor:
+    if isinstance(value, torch.Tensor):
+      t = value.to(self.device, torch.float32, non_blocking=True)
+    else:
+      t = torch.from_numpy(np.ascontiguousarray(np.asarray(value, dtype=np.float32))).to(self.device, non_blocking=True)
+    if t.numel() != numel:
+      raise ValueError("DeviceRecorder.append: %s has %d values, expected %d" % (what, t.numel(), numel))
+    return t.reshape(-1)
+
+  def append(self, *, lidar, velocity, is_at_traffic_light, traffic_light_state, location, rotation) -> None:
+    from oatomobile_amd import _lib
+    n = self._n
+    if n >= self.capacity:
+      raise IndexError("DeviceRecorder: frame %d exceeds the capacity of %d frames" % (n + 1, self.capacity))
+    if tuple(np.shape(lidar)) != (self.H, self.W, self.C):
+      raise ValueError("DeviceRecorder.append: lidar has shape %s, expected %s" % (tuple(np.shape(lidar)), (self.H, self.W, self.C)))
+    bev = self._f32(lidar, self.H * self.W * self.C, "lidar").contiguous()
+    self.vec[n, 0:3] = self._f32(velocity, 3, "velocity")
+    self.vec[n, 3:4] = self._f32(is_at_traffic_light, 1, "is_at_traffic_light")
+    self.vec[n, 4:5] = self._f32(traffic_light_state, 1, "traffic_light_state")
+    self.location[n] = self._f32(location, 3, "location")
+    self.rotation[n] = self._f32(rotation, 3, "rotation")
+    with torch.cuda.device(self.device):  # stateless entry point: launches on the current device
+      _lib.check(_lib.load().rip_code_bev_u8(_lib.ptr(bev), 1, self.H, self.W, self.C, _lib.ptr(self.lut), self.n_values,
+                                             _lib.ptr(self.codes[n], torch.uint8), _lib.ptr(self._miss, torch.int32),
+                                             _lib.current_stream(self.device)))
+    self._episodes.append(self._episode)
+    self._n = n + 1
+
+  def end_episode(self) -> None:
+    """Marks an episode boundary: no window reaches across it."""
+    self._episode += 1
+
+  def window_frames(self, num_frame_skips: int = 1) -> np.ndarray:
+    """`range(P, len(episode) - L, num_frame_skips)` of every recorded episode, as indices into the recording."""
+    episodes = np.asarray(self._episodes, np.int64)
+    out = []
+    for e in np.unique(episodes):
+      idx = np.flatnonzero(episodes == e)  # contiguous: frames are appended in order
+      out.append(idx[0] + np.arange(self.P, idx.size - self.L, int(num_frame_skips), dtype=np.int64))
+    return np.concatenate(out).astype(np.int32) if out else np.empty((0,), np.int32)
+
+  def cache(self, num_frame_skips: int = 1) -> "DeviceCache":
+    if int(num_frame_skips) < 1:
+      raise ValueError("DeviceRecorder.cache: num_frame_skips must be >= 1")
+    frames = self.window_frames(num_frame_skips)
+    if frames.size == 0:
+      raise ValueError("DeviceRecorder.cache: no frame of the %d recorded has a full window (past %d, future %d)" %
+                       (self._n, self.P, self.L))
+    dev, n = self.device, self._n
+    with torch.cuda.device(dev):
+      rows = torch.from_numpy(frames).to(dev)
+      episode = torch.from_numpy(np.asarray(self._episodes, np.int32)).to(dev)
+      out = _hindsight_launch(self.location[:n], self.rotation[:n], episode, rows, self.L, self.P, self.G, self.goal_stride,
+                              {"future_xy", "mode"})
+      index = rows.to(torch.int64)
+      codes, vec = self.codes.index_select(0, index), self.vec.index_select(0, index)
+      misses = int(self._miss.item()) & 0xffffffff  # the one synchronisation
+    if misses:
+      raise ValueError("DeviceRecorder.cache: %d recorded BEV cells hold a value that is not in the table" % misses)
+    self.frames = frames
+    return DeviceCache.from_tensors(codes, self.lut, vec, out["future_xy"], out["mode"])
 
 
 def replay_cache(agent, cache: "PackedCache", batch_size: int, interpolate: bool = False, begin: int = 0,

@@ -90,6 +90,39 @@ int rip_destroy(rip_handle* h);
  * running statistics = eval mode) is folded into the preceding conv here. */
 int rip_load_model(rip_handle* h, int k, const float* packed_host, size_t numel);
 
+/* The same load from DEVICE memory, for weights that were trained on the device
+ * (oatomobile_amd/train.py: DIMTrainer.params has the layout of `packed_host`
+ * above).  `packed_dev` = `numel` floats on the handle's device.  The BatchNorm
+ * fold (in double, as the host load does it) and every re-layout of the host
+ * load run as four kernels on `stream`, behind whatever the caller ordered
+ * there, and write slot `k` of the handle's weight buffers in place: every
+ * byte equals what the host load writes for the same values.  No device-wide
+ * synchronise, no host fold, no pageable copy.  The call then waits for
+ * `stream` alone, once, to read the member's two kernel-selection flags
+ * through a pinned word the handle owns -- so it cannot be captured into a
+ * graph -- and marks the member loaded.  Pipelines captured over the handle
+ * stay valid (the buffers do not move) unless one of the two flags changed:
+ * kernel selection is part of a capture (see the flags call below).
+ * RIP_EINVAL before any launch for a NULL argument, `k` outside [0, K) or a
+ * wrong `numel`. */
+int rip_load_model_device(rip_handle* h, int k, const float* packed_dev, size_t numel, rip_stream_t stream);
+
+/* Inspection: copies member `k`'s slice of weight buffer `which` to `dst_dev`
+ * (device memory of `cap_bytes` bytes) on `stream` and reports its size in
+ * `*bytes` (may be NULL).  `dst_dev` == NULL only reports the size.  which:
+ * 0 folded fp32 blob, 1 its bf16 copy, 2 the fp32 blob with bf16-valued
+ * depthwise taps, 3 chunk records of the split-f16 tile blocks, 4 operand
+ * fragments of the split-f16 row blocks, 5 flow weights, 6 operands of the
+ * fp32-MFMA search, 7 operands of the split-f16 search. */
+int rip_peek_weights(rip_handle* h, int k, int which, void* dst_dev, size_t cap_bytes, size_t* bytes, rip_stream_t stream);
+
+/* The two per-member flags a load computes and kernel selection reads:
+ * `*split_wmax` = the largest magnitude of the flow's GRU / head weights (the
+ * split-f16 search needs it below 200; a NaN or infinite weight reports 200),
+ * `*enc_split_ok` = 1 when every folded pointwise weight is below 240 in
+ * magnitude (the fp32 encoder's split-f16 blocks).  Either may be NULL. */
+int rip_model_flags(const rip_handle* h, int k, float* split_wmax, int* enc_split_ok);
+
 /* R2 — ImitativeModel.transform on `lidar` (dim/model.py:245-251 ->
  * torch/transforms.py:34-49): bilinear (H,W)->(out_hw,out_hw) with
  * align_corners=True, then swap H and W.  in: [B,C,H,W] (channels_last=0) or

@@ -19,6 +19,9 @@ SIGNATURES = [
     ("rip_create", c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
     ("rip_destroy", c_int, [c_void_p]),
     ("rip_load_model", c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    ("rip_load_model_device", c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    ("rip_peek_weights", c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, POINTER(c_size_t), c_void_p]),
+    ("rip_model_flags", c_int, [c_void_p, c_int, POINTER(c_float), POINTER(c_int)]),
     ("rip_transform", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("rip_encode", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("rip_encode_tap", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
@@ -118,6 +121,7 @@ ENC_VAR_IRB_ROUND3, ENC_VAR_FRONT_ROUND3, ENC_VAR_ROWS_F5_7, ENC_VAR_F17_LAYERWI
 ENC_VAR_FP32_LAYERWISE = 16  # fp32 encoder without the split-f16 tile blocks (encoder_split_tile.hip)
 TRAIN_OPT_DETERMINISTIC = 1  # RIP_TRAIN_OPT_DETERMINISTIC of include/rip_hip.h (rip_train_set_option)
 STAT_MEAN, STAT_VARIANCE, STAT_MIN, STAT_MAX, STAT_SLOTS = 0, 1, 2, 3, 4  # RIP_STAT_* of include/rip_hip.h
+SPLIT_W_LIMIT = 200.0  # csrc/flow.h: a member with a flow weight of this magnitude keeps the fp32-MFMA search
 SEARCH_KERNELS = {"auto": 0, "chain": 1, "phase": 3, "split": 4, "pair": 5}  # "pair": split-f16, paired workgroup shape forced
 
 
@@ -220,6 +224,43 @@ class Handle:
     import numpy as np
     packed = np.ascontiguousarray(packed, dtype=np.float32)
     check(self._lib.rip_load_model(self._h, k, packed.ctypes.data_as(c_void_p), packed.size))
+
+  def load_model_device(self, k: int, packed) -> None:
+    """`rip_load_model_device`: member `k` from a contiguous float32 tensor of `arch.packed_numel(C)` elements on the
+    handle's device (the layout of `load_model`'s vector; `DIMTrainer.params` has it), on torch's current stream.  The
+    fold and the re-layouts run on the device; the call waits for that stream once, for the member's flags."""
+    import torch
+    from oatomobile_amd import arch
+    if not isinstance(packed, torch.Tensor):
+      raise TypeError("load_model_device: expected a torch.Tensor, got %s" % type(packed).__name__)
+    if not packed.is_cuda or packed.device.index != self.device_index:
+      raise ValueError("load_model_device: the weights must be on cuda:%d, got %s" % (self.device_index, packed.device))
+    want = arch.packed_numel(self.in_channels)
+    if packed.dim() != 1 or packed.numel() != want:
+      raise ValueError("load_model_device: expected %d packed floats (in_channels=%d), got shape %s" %
+                       (want, self.in_channels, tuple(packed.shape)))
+    check(self._lib.rip_load_model_device(self._h, k, ptr(packed), packed.numel(), self.stream()))
+
+  def peek_weights(self, k: int, which: int):
+    """`rip_peek_weights`: member `k`'s slice of weight buffer `which` (0..7, include/rip_hip.h) as a uint8 device tensor."""
+    import torch
+    n = c_size_t(0)
+    check(self._lib.rip_peek_weights(self._h, k, which, None, 0, ctypes.byref(n), None))
+    out = torch.empty(n.value, dtype=torch.uint8, device=torch.device("cuda", self.device_index))
+    check(self._lib.rip_peek_weights(self._h, k, which, ptr(out, torch.uint8), n.value, None, self.stream()))
+    return out
+
+  def kernel_selection(self, k: int):
+    """What of `model_flags` kernel selection reads: (the split-f16 search may take member `k`, the fp32 encoder's
+    split-f16 blocks may).  A pipeline captured over the handle stays valid while this does not change."""
+    wmax, ok = self.model_flags(k)
+    return wmax < SPLIT_W_LIMIT, ok
+
+  def model_flags(self, k: int):
+    """`rip_model_flags` -> (split_wmax, enc_split_ok) of member `k`: what kernel selection reads."""
+    wmax, ok = c_float(0.0), c_int(0)
+    check(self._lib.rip_model_flags(self._h, k, ctypes.byref(wmax), ctypes.byref(ok)))
+    return wmax.value, bool(ok.value)
 
   def set_option(self, option: int, value: int) -> None:
     check(self._lib.rip_set_option(self._h, option, value))

@@ -250,6 +250,61 @@ class RIPAgent(SetPointAgent):
         changed = True
     return changed
 
+  def load_member(self, k: int, source) -> None:
+    """Hands member `k` new weights ON THE DEVICE: `source` is a `DIMTrainer` (its `.params`) or a contiguous float32
+    tensor of `arch.packed_numel(C)` elements on this agent's device, in the layout of `ImitativeModel.packed_weights()`.
+    One `rip_load_model_device` per handle (this agent's, and the cached replay twin's if there is one) on torch's
+    current stream, behind the training step that produced the weights: no copy to the host, no host fold, no
+    device-wide synchronise.  The bytes that land in the handle equal those of `trainer.sync_to_model()` +
+    `agent.refresh()`.
+
+    The `ImitativeModel` objects are NOT touched: `agent.refresh()` or a model's `refresh()` / `load_state_dict()` goes
+    back to THEIR weights, and `trainer.sync_to_model()` remains the way to bring trained weights into them.  The
+    captured one-observation pipelines are kept (the weight buffers do not move) unless one of the member's two
+    kernel-selection flags changed (`Handle.kernel_selection`): kernel selection is part of a capture, so they are dropped
+    then and re-captured by the next call.  `ValueError` for a source on another device, with another channel count
+    or length; `TypeError` for anything else, a `CILTrainer` included."""
+    from oatomobile_amd import train as _train
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < len(self._models):
+      raise ValueError("load_member: member index %r outside [0, %d)" % (k, len(self._models)))
+    if isinstance(source, _train.DIMTrainer):
+      if source._C != self._in_channels:
+        raise ValueError("load_member: the trainer's model has %d BEV channels, this agent's %d" % (source._C, self._in_channels))
+      packed = source.params
+    elif isinstance(source, torch.Tensor):
+      packed = source
+    else:
+      raise TypeError("load_member: `source` must be a DIMTrainer or a packed float32 device tensor, got %s%s" %
+                      (type(source).__name__, " (CIL weights are another model's)" if isinstance(source, _train.CILTrainer) else ""))
+    want = arch.packed_numel(self._in_channels)
+    if packed.dim() != 1 or packed.numel() != want:
+      raise ValueError("load_member: expected %d packed floats (in_channels=%d), got shape %s" %
+                       (want, self._in_channels, tuple(packed.shape)))
+    if packed.dtype != torch.float32 or not packed.is_contiguous():
+      raise ValueError("load_member: the weights must be a contiguous float32 tensor, got %s%s" %
+                       (packed.dtype, "" if packed.is_contiguous() else " (not contiguous)"))
+    if not packed.is_cuda or packed.device != self._device:
+      raise ValueError("load_member: the weights must be on %s, got %s" % (self._device, packed.device))
+    k = int(k)
+    if self._sync_weights():  # (members whose model changed go first, so that this load is not mistaken for theirs)
+      self._online = {}
+    before = self._handle.kernel_selection(k)
+    self._handle.load_model_device(k, packed)
+    self._versions[k] = self._models[k]._version
+    self._eager_pending = True
+    if self._handle.kernel_selection(k) != before:
+      self._online = {}
+    if self._replay_twin is not None:
+      self._replay_twin.load_member(k, packed)
+
+  def load_members(self, sources) -> None:
+    """`load_member(k, sources[k])` for every member; `None` leaves a member as it is."""
+    if len(sources) != len(self._models):
+      raise ValueError("load_members: %d sources for %d members" % (len(sources), len(self._models)))
+    for k, source in enumerate(sources):
+      if source is not None:
+        self.load_member(k, source)
+
   def twin(self) -> "RIPAgent":
     """A second agent over the SAME models and latent starts with a handle (weights snapshot + scratch) of its own: two
     handles on two streams let one batch's encoder run beside another batch's search (`replay.replay_cache(streams=2)`).

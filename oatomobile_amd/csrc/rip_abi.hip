@@ -17,6 +17,7 @@
 #include "encoder.h"
 #include "flow.h"
 #include "train.h"
+#include "weights_pack.h"
 
 using namespace rip;
 
@@ -74,6 +75,11 @@ struct rip_handle {
   int* mega_status = nullptr;            // pinned host word: non-zero = the protocol failed, results of that call invalid
   bool mega_reported = false;            // the failure has been handed to the caller (rip_encoder_status or an error)
   unsigned long long* mega_ticks = nullptr;  // development (RIP_MEGA_TICKS=1): per-layer wall clock of model 0
+  // rip_load_model_device (weights_pack.hip): index tables of the device packers, their flag words on the device and
+  // the pinned word the flags come back through
+  PackPlan pack;
+  unsigned* pack_flags = nullptr;       // [4]
+  unsigned* pack_flags_host = nullptr;  // [4] pinned
 };
 
 // Makes the handle's device current for one entry point and restores the caller's on exit.
@@ -288,6 +294,18 @@ int rip_create(rip_handle** out, int K, int in_channels, int max_batch, int max_
     ALLOC(tmp, (h->tape_bytes + 3) / 4);
     h->tape = tmp;
   }
+  {
+    float* tmp = nullptr;
+    ALLOC(tmp, 4);
+    h->pack_flags = reinterpret_cast<unsigned*>(tmp);
+    hipError_t e_ = hipHostMalloc((void**)&h->pack_flags_host, 4 * sizeof(unsigned), hipHostMallocDefault);
+    if (e_ != hipSuccess) {
+      h->pack_flags_host = nullptr;
+      rip_destroy(h);
+      return fail(RIP_EHIP, "hipHostMalloc(16 B) failed: %s", hipGetErrorString(e_));
+    }
+  }
+  h->pack = build_pack_plan(h->plan);
 #undef ALLOC
   *out = h;
   return RIP_OK;
@@ -312,6 +330,8 @@ int rip_destroy(rip_handle* h) {
     (void)hipFree(h->mega_ticks);
   }
   if (h->mega_status != nullptr) (void)hipHostFree(h->mega_status);
+  if (h->pack_flags_host != nullptr) (void)hipHostFree(h->pack_flags_host);
+  if (h->pack_flags != nullptr) (void)hipFree(h->pack_flags);
   if (h->mega_sync != nullptr) (void)hipFree(h->mega_sync);
   if (h->mega_arena != nullptr) (void)hipFree(h->mega_arena);
   float* ptrs[] = {h->enc_w, h->enc_wt, reinterpret_cast<float*>(h->enc_wh), reinterpret_cast<float*>(h->enc_wc), reinterpret_cast<float*>(h->enc_wr), h->flow_w, h->mfma_w, reinterpret_cast<float*>(h->split_w), h->bufs[0], h->bufs[1], h->bufs[2], h->bufs[3], h->visual,
@@ -466,6 +486,64 @@ int rip_load_model(rip_handle* h, int k, const float* packed_host, size_t numel)
   HIP_TRY(hipMemcpy(h->mfma_w + (size_t)k * MW_SIZE, mw.data(), mw.size() * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->split_w + (size_t)k * MH_SIZE, mh.data(), mh.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   h->loaded[k] = true;
+  return RIP_OK;
+}
+
+int rip_load_model_device(rip_handle* h, int k, const float* packed_dev, size_t numel, rip_stream_t stream) {
+  REQUIRE(h != nullptr && packed_dev != nullptr, "NULL argument");
+  REQUIRE(k >= 0 && k < h->K, "model index %d outside [0,%d)", k, h->K);
+  if (!h->pack.ok) return fail(RIP_ESTATE, "the device packers do not know this encoder plan's operand layouts");
+  REQUIRE(numel == h->pack.numel, "packed state_dict has the wrong length (got %zu floats, %zu expected)", numel, h->pack.numel);
+  ENTER(h, stream);
+  TraceRange range_("rip_load_model_device");
+  PackTargets t;
+  t.enc_w = h->enc_w + (size_t)k * h->plan.blob_floats;
+  t.enc_wh = h->enc_wh + (size_t)k * h->plan.blob_floats;
+  t.enc_wt = h->enc_wt + (size_t)k * h->plan.blob_floats;
+  t.enc_wc = h->enc_wc + (size_t)k * h->plan.split_tiles.total;
+  t.enc_wr = h->enc_wr + (size_t)k * h->plan.split_rows.total;
+  t.flow_w = h->flow_w + (size_t)k * FW_SIZE;
+  t.mfma_w = h->mfma_w + (size_t)k * MW_SIZE;
+  t.split_w = h->split_w + (size_t)k * MH_SIZE;
+  t.flags = h->pack_flags;
+  h->loaded[k] = false;  // (stays so if anything below fails: the slot is then partly written)
+  HIP_TRY(launch_pack_weights(h->plan, h->pack, packed_dev, t, (hipStream_t)stream));
+  // the two host-side flags: through the pinned word, waiting for this stream alone
+  HIP_TRY(hipMemcpyAsync(h->pack_flags_host, h->pack_flags, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  float wmax;
+  std::memcpy(&wmax, &h->pack_flags_host[0], 4);
+  h->split_wmax[k] = h->pack_flags_host[1] != 0u ? SPLIT_W_LIMIT : wmax;  // (a NaN / infinite weight counts as out of range)
+  h->enc_split_ok[k] = h->pack_flags_host[2] == 0u;
+  h->loaded[k] = true;
+  return RIP_OK;
+}
+
+int rip_peek_weights(rip_handle* h, int k, int which, void* dst_dev, size_t cap_bytes, size_t* bytes, rip_stream_t stream) {
+  REQUIRE(which >= 0 && which <= 7, "unknown weight buffer %d (0 enc_w, 1 enc_wh, 2 enc_wt, 3 enc_wc, 4 enc_wr, 5 flow_w, 6 mfma_w, 7 split_w)", which);
+  REQUIRE(h != nullptr, "handle is NULL");
+  REQUIRE(dst_dev != nullptr || bytes != nullptr, "NULL argument: nothing to report into");
+  REQUIRE(k >= 0 && k < h->K, "model index %d outside [0,%d)", k, h->K);
+  const size_t blob = h->plan.blob_floats, tiles = h->plan.split_tiles.total, rows = h->plan.split_rows.total;
+  const size_t sizes[8] = {blob * 4, blob * 2, blob * 4, tiles * 2, rows * 2, (size_t)FW_SIZE * 4, (size_t)MW_SIZE * 4, (size_t)MH_SIZE * 4};
+  const char* bases[8] = {(const char*)h->enc_w, (const char*)h->enc_wh, (const char*)h->enc_wt, (const char*)h->enc_wc,
+                          (const char*)h->enc_wr, (const char*)h->flow_w, (const char*)h->mfma_w, (const char*)h->split_w};
+  if (bytes != nullptr) *bytes = sizes[which];
+  if (dst_dev == nullptr) return RIP_OK;
+  if (!h->loaded[k]) return fail(RIP_ESTATE, "model %d has no weights (call rip_load_model first)", k);
+  REQUIRE(cap_bytes >= sizes[which], "cap_bytes=%zu, buffer %d of a model has %zu bytes", cap_bytes, which, sizes[which]);
+  ENTER(h, stream);
+  if (sizes[which] > 0)
+    HIP_TRY(hipMemcpyAsync(dst_dev, bases[which] + (size_t)k * sizes[which], sizes[which], hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return RIP_OK;
+}
+
+int rip_model_flags(const rip_handle* h, int k, float* split_wmax, int* enc_split_ok) {
+  REQUIRE(h != nullptr, "handle is NULL");
+  REQUIRE(k >= 0 && k < h->K, "model index %d outside [0,%d)", k, h->K);
+  if (!h->loaded[k]) return fail(RIP_ESTATE, "model %d has no weights (call rip_load_model first)", k);
+  if (split_wmax != nullptr) *split_wmax = h->split_wmax[k];
+  if (enc_split_ok != nullptr) *enc_split_ok = h->enc_split_ok[k] ? 1 : 0;
   return RIP_OK;
 }
 

@@ -404,6 +404,12 @@ class DIMTrainer(_PackedTrainer):
     return super().sync_to_model()
 
 
+  def publish(self, agent, k: int) -> None:
+    """`agent.load_member(k, self)`: hands the current parameters to member `k` of a live `RIPAgent` on the device,
+    behind the steps already issued on the current stream.  The wrapped model is not touched (`sync_to_model`)."""
+    agent.load_member(k, self)
+
+
 class CILTrainer(_PackedTrainer):
   """The behavioural-cloning step of oatomobile/baselines/torch/cil/train.py on one `BehaviouralModel`, one device:
 

@@ -113,6 +113,19 @@ SIGNATURES = [
 ]
 ABI_VERSION = 4
 
+# The extension header include/rip_head.h (the K-member head step on cached features): a table and a version of its
+# own, resolved by the same `load()`; `SIGNATURES` and `ABI_VERSION` above are include/rip_hip.h's alone.
+HEAD_SIGNATURES = [
+    ("rip_head_abi_version", c_int, []),
+    ("rip_head_numel", c_size_t, []),
+    ("rip_head_workspace_bytes", c_size_t, [c_int, c_int]),
+    ("rip_head_forward_backward", c_int, [
+        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p
+    ]),
+]
+HEAD_ABI_VERSION = 1
+
 ALGORITHMS = {"WCM": 0, "MA": 1, "BCM": 2}
 ENC_DTYPES = {"fp32": 0, "bf16": 1}
 OPT_SEARCH_KERNEL, OPT_ENCODER_FUSED, OPT_SEARCH_REGROUP, OPT_ENCODER_MEGA, OPT_DEBUG_ENCODER_FAULT = 0, 1, 2, 3, 4
@@ -154,7 +167,7 @@ def load() -> ctypes.CDLL:
         "oatomobile_amd: %s is missing — the HIP extension is not built "
         "(run `python -c \"import __graft_entry__ as g; g.build()\"`). There is no CPU fallback." % LIB_PATH)
   lib = ctypes.CDLL(LIB_PATH)
-  for name, restype, argtypes in SIGNATURES:
+  for name, restype, argtypes in SIGNATURES + HEAD_SIGNATURES:
     fn = getattr(lib, name)  # AttributeError if the .so is stale
     fn.restype = restype
     fn.argtypes = argtypes

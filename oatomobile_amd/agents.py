@@ -394,6 +394,60 @@ class RIPAgent(SetPointAgent):
                                   _lib.ptr(st), stream))
     return _plan_stats(q, st)
 
+  def _features(self, visual: torch.Tensor, vec: torch.Tensor):
+    b, K = visual.shape[0], len(self._models)
+    feat = torch.empty(K, b, arch.NUM_FEATURES, device=self._device, dtype=torch.float32)
+    z = torch.empty(K, b, arch.HIDDEN_SIZE, device=self._device, dtype=torch.float32)
+    _lib.check(_lib.load().rip_encode(self._handle.raw, _lib.ptr(visual), _lib.ptr(vec), b, 0, K, self._enc_dtype, _lib.ptr(z),
+                                      _lib.ptr(feat), self._handle.stream()))
+    return feat, z
+
+  def features_batch(self, lidar: torch.Tensor, vec: torch.Tensor):
+    """The K members' encoder outputs on a batch: lidar [B,H,W,C], vec [B,5] as `plan_batch` -> `(feat [K,B,128],
+    z [K,B,64])` — the classifier logits of each member's MobileNetV2 and the merger's output on them, from this agent's
+    handle and `encoder_dtype`.  `rip_transform`, then one `rip_encode` with `feat_dev`.  What `train.HeadTrainer`
+    trains on (`replay.FeatureCache` holds them for a whole cache); the encoder's kernel selection keys on B * K, so the
+    bits are those of this batch composition."""
+    self._check_batch(lidar, vec, None, what="features_batch", pair_only=True)
+    if self._sync_weights():
+      self._online = {}
+    lidar, vec = lidar.contiguous(), vec.contiguous()
+    b, H, W = lidar.shape[0], lidar.shape[1], lidar.shape[2]
+    visual = torch.empty(b, self._in_channels, arch.INPUT_HW, arch.INPUT_HW, device=self._device, dtype=torch.float32)
+    self._eager_pending = True
+    with torch.cuda.device(self._device):  # rip_transform is stateless: it launches on the current device
+      _lib.check(_lib.load().rip_transform(_lib.ptr(lidar), b, self._in_channels, H, W, 1, arch.INPUT_HW, _lib.ptr(visual),
+                                           self._handle.stream()))
+    return self._features(visual, vec)
+
+  def features_batch_coded(self, codes: torch.Tensor, lut: torch.Tensor, vec: torch.Tensor):
+    """`features_batch` on a CODED BEV (codes [B,H,W,C] uint8 into lut [256], as `plan_batch_coded`): the table is
+    applied by `rip_gather_batch_u8` (rows 0 .. B - 1), whose image equals `rip_transform`'s on the decoded BEV bit for
+    bit, then one `rip_encode` with `feat_dev`."""
+    dev = self._device
+    if not (isinstance(codes, torch.Tensor) and codes.is_cuda and codes.device == dev and codes.dtype == torch.uint8):
+      raise ValueError("features_batch_coded: `codes` must be a uint8 tensor on %s" % (dev,))
+    _lib.expect_shape(codes, (None, None, None, self._in_channels), "codes")
+    b = codes.shape[0]
+    if b < 1 or b > self._max_batch:
+      raise ValueError("features_batch_coded: batch %d outside [1, max_batch=%d]" % (b, self._max_batch))
+    _lib.expect_shape(lut, (256,), "lut")
+    _lib.expect_shape(vec, (b, 5), "vec")
+    if self._sync_weights():
+      self._online = {}
+    codes, vec = codes.contiguous(), vec.contiguous()
+    visual = torch.empty(b, self._in_channels, arch.INPUT_HW, arch.INPUT_HW, device=dev, dtype=torch.float32)
+    rows = torch.arange(b, device=dev, dtype=torch.int64)
+    vec_out = torch.empty(b, 5, device=dev)
+    future = torch.zeros(b, arch.T, 2, device=dev)  # the gather kernel's target slot: not used here
+    self._eager_pending = True
+    with torch.cuda.device(dev):
+      _lib.check(_lib.load().rip_gather_batch_u8(
+          _lib.ptr(codes, torch.uint8), _lib.ptr(lut), _lib.ptr(rows, torch.int64), b, b, self._in_channels, codes.shape[1],
+          codes.shape[2], arch.INPUT_HW, _lib.ptr(vec), _lib.ptr(future), arch.T, arch.T, 1, None, _lib.ptr(visual),
+          _lib.ptr(vec_out), _lib.ptr(torch.empty_like(future)), None, self._handle.stream()))
+    return self._features(visual, vec)
+
   def plan_batch(self, lidar: torch.Tensor, vec: torch.Tensor, goal: torch.Tensor,
                  return_loss: bool = False, interpolate: bool = False, out: Optional[torch.Tensor] = None,
                  return_stats: bool = False):

@@ -1,6 +1,7 @@
 // C ABI of librip_hip.so (include/rip_hip.h): handle management, checkpoint folding, argument
 // validation and kernel launch sequencing.  No torch types cross this boundary.
 #include "../../include/rip_hip.h"
+#include "../../include/rip_head.h"
 
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 
 #include "encoder.h"
 #include "flow.h"
+#include "head_train.h"
 #include "train.h"
 #include "weights_pack.h"
 
@@ -23,6 +25,7 @@ using namespace rip;
 
 static_assert(RIP_MAX_MODELS == rip::MAX_MODELS, "header / kernel constant mismatch");
 static_assert(RIP_MAX_GOALS == rip::MAX_GOALS, "header / kernel constant mismatch");
+static_assert(RIP_HEAD_NUMEL == rip::HEAD_NUMEL && RIP_HEAD_FEATURES == 128, "rip_head.h / kernel constant mismatch");
 static_assert(RIP_ALGO_WCM == rip::ALGO_WCM && RIP_ALGO_MA == rip::ALGO_MA && RIP_ALGO_BCM == rip::ALGO_BCM, "algo ids");
 
 struct rip_handle {
@@ -1339,6 +1342,57 @@ int rip_train_adam(float* params_dev, const float* grads_dev, float* m_dev, floa
   if (scope.err != hipSuccess) return fail(RIP_EHIP, "hipSetDevice(%d) failed: %s", attr.device, hipGetErrorString(scope.err));
   HIP_TRY(trainer_adam(params_dev, grads_dev, m_dev, v_dev, trainable_dev, numel, step, lr, beta1, beta2, eps, weight_decay,
                        (hipStream_t)stream));
+  return RIP_OK;
+}
+
+// ---------------- include/rip_head.h: the K-member head step on cached features (head_train.hip) ----------------
+int rip_head_abi_version(void) { return RIP_HEAD_ABI_VERSION; }
+
+size_t rip_head_numel(void) { return HEAD_NUMEL; }
+
+size_t rip_head_workspace_bytes(int K, int max_batch) {
+  return K >= 1 && K <= RIP_MAX_MODELS && max_batch >= 1 ? head_workspace_bytes(K, max_batch) : 0;
+}
+
+int rip_head_forward_backward(const float* head_dev, float* grads_dev, const float* feat_dev, const float* vec_dev,
+                              int64_t n, const int64_t* rows_dev, const float* y_dev, const float* future_dev, int L,
+                              int stride, const float* noise_dev, int K, int B, int max_batch, void* workspace_dev,
+                              float* q_rows_dev, float* loss_dev, float* z_dev, rip_stream_t stream) {
+  REQUIRE(head_dev != nullptr && feat_dev != nullptr && vec_dev != nullptr && q_rows_dev != nullptr && loss_dev != nullptr,
+          "NULL argument (head, feat, vec, q_rows and loss are required)");
+  REQUIRE((y_dev != nullptr) != (future_dev != nullptr), "NULL target: exactly one of y_dev and future_dev must be given");
+  REQUIRE(noise_dev == nullptr || future_dev != nullptr, "noise_dev goes with future_dev (a dense y_dev is taken as it is)");
+  REQUIRE(K >= 1 && K <= RIP_MAX_MODELS, "K=%d outside [1,%d]", K, RIP_MAX_MODELS);
+  REQUIRE(max_batch >= 1 && B >= 1 && B <= max_batch, "B=%d outside [1,max_batch=%d]", B, max_batch);
+  REQUIRE(n >= 1, "n=%lld cache rows: must be >= 1", (long long)n);
+  REQUIRE(rows_dev != nullptr || n == B, "rows_dev is NULL (the identity) but n=%lld != B=%d", (long long)n, B);
+  if (future_dev != nullptr)
+    REQUIRE(stride >= 1 && L >= 1 && (L + stride - 1) / stride == RIP_T, "stride=%d over L=%d waypoints gives %d steps, T=%d needed",
+            stride, L, stride >= 1 && L >= 1 ? (L + stride - 1) / stride : 0, RIP_T);
+  REQUIRE(grads_dev == nullptr || workspace_dev != nullptr, "NULL workspace: a gradient call needs rip_head_workspace_bytes(K, max_batch) bytes");
+  REQUIRE((reinterpret_cast<uintptr_t>(head_dev) & 15) == 0, "head_dev must be 16-byte aligned");
+  hipPointerAttribute_t attr;
+  HIP_TRY(hipPointerGetAttributes(&attr, head_dev));
+  DeviceScope scope(attr.device);
+  if (scope.err != hipSuccess) return fail(RIP_EHIP, "hipSetDevice(%d) failed: %s", attr.device, hipGetErrorString(scope.err));
+  TraceRange range_(grads_dev != nullptr ? "rip_head_forward_backward" : "rip_head_forward");
+  HeadArgs a;
+  a.head = head_dev;
+  a.feat = feat_dev;
+  a.vec = vec_dev;
+  a.y = y_dev;
+  a.future = future_dev;
+  a.noise = noise_dev;
+  a.rows = reinterpret_cast<const long long*>(rows_dev);
+  a.n = n;
+  a.K = K;
+  a.B = B;
+  a.L = L;
+  a.stride = stride;
+  a.q_rows = q_rows_dev;
+  a.z = z_dev;
+  a.loss = loss_dev;
+  HIP_TRY(launch_head_step(a, grads_dev, workspace_dev, (hipStream_t)stream));
   return RIP_OK;
 }
 

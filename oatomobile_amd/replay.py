@@ -1043,3 +1043,59 @@ def predict_cache(agent, data: "DeviceCache", batch_size: int, num_samples: int,
     for tag, k in (("1", 1), ("k", top_k)):  # means in float64 of the float32 rows
       out["min_%s_%s" % (name, tag)] = float(prediction.min_over_k(out[name], k).astype(np.float64).mean()) if n else float("nan")
   return out
+
+
+class FeatureCache:
+  """The K members' encoder outputs over a whole `DeviceCache`, what `train.HeadTrainer` trains on:
+
+      cache = FeatureCache.build(agent, data, batch_size=128)   # feat [K,n,128] on the device, 2 KB per observation at K = 4
+      cache.verify(agent)                                        # a few rows recomputed and compared bit for bit
+
+  `feat[k, i]` is member k's MobileNetV2 logits on observation i (`RIPAgent.features_batch_coded` on the cache's rows
+  [i0, i0 + batch_size) in order); `vec` [n,5] and `future` [n,L,2] are the `DeviceCache`'s own tensors (shared, not
+  copied).  The cache is valid only while the members' ENCODERS are unchanged: a head update (`HeadTrainer.publish`)
+  leaves it valid, anything that loads other encoder weights into the agent does not, and nothing invalidates it
+  automatically — `verify` is the check.  The encoder's kernel selection keys on B * K, so the features are
+  reproducible bit for bit only at the same batch composition: `verify` recomputes the batches of `batch_size` rows
+  the cache was built with."""
+
+  def __init__(self, feat: torch.Tensor, vec: torch.Tensor, future: torch.Tensor, batch_size: int, data: "DeviceCache") -> None:
+    self.feat, self.vec, self.future, self.batch_size, self.data = feat, vec, future, int(batch_size), data
+
+  def __len__(self) -> int:
+    return int(self.feat.shape[1])
+
+  @staticmethod
+  def _batch(agent, data: "DeviceCache", i0: int, i1: int) -> torch.Tensor:
+    feat, _ = agent.features_batch_coded(data.codes[i0:i1], data.lut, data.vec[i0:i1])
+    return feat
+
+  @classmethod
+  def build(cls, agent, data: "DeviceCache", batch_size: int) -> "FeatureCache":
+    dev = agent._device
+    if data.device != dev:
+      raise RuntimeError("FeatureCache.build: the cache is on %s, the agent on %s" % (data.device, dev))
+    if data.channels != agent._in_channels:
+      raise ValueError("FeatureCache.build: the cache has %d BEV channels, the agent expects %d" % (data.channels, agent._in_channels))
+    batch_size = int(batch_size)
+    if batch_size < 1 or batch_size > agent._max_batch:
+      raise ValueError("FeatureCache.build: batch_size %d outside [1, max_batch=%d]" % (batch_size, agent._max_batch))
+    n, K = len(data), len(agent._models)
+    feat = torch.empty((K, n, 128), device=dev, dtype=torch.float32)
+    for i0 in range(0, n, batch_size):
+      i1 = min(n, i0 + batch_size)
+      feat[:, i0:i1] = cls._batch(agent, data, i0, i1)
+    return cls(feat, data.vec, data.future, batch_size, data)
+
+  def verify(self, agent, rows: int = 8) -> bool:
+    """Recomputes the build batches of `rows` rows spread evenly over the cache with `agent` and compares them with the
+    cached features bit for bit (one synchronisation).  False = the members' encoders are not the ones the cache was
+    built with (or the agent's batch composition differs): rebuild."""
+    n = len(self)
+    picks = sorted({(j * n) // max(1, int(rows)) for j in range(max(1, int(rows)))})
+    same = torch.ones((), dtype=torch.bool, device=self.feat.device)
+    for b0 in sorted({(i // self.batch_size) * self.batch_size for i in picks}):
+      b1 = min(n, b0 + self.batch_size)
+      fresh = self._batch(agent, self.data, b0, b1)
+      same = same & (fresh.view(torch.int32) == self.feat[:, b0:b1].view(torch.int32)).all()
+    return bool(same)

@@ -492,3 +492,208 @@ class CILTrainer(_PackedTrainer):
     """Writes the trained weights into the wrapped `BehaviouralModel`: its next `forward` (and every `CILAgent`
     holding it) runs on them."""
     return super().sync_to_model()
+
+
+class HeadTrainer:
+  """The density heads of ALL members of a `RIPAgent`'s ensemble trained on cached encoder features, one step for the K
+  members in four launches whatever K and the batch (`rip_head_forward_backward` of include/rip_head.h: forward /
+  backward, weight gradients, losses; then `rip_train_adam` on the flattened heads):
+
+      cache = replay.FeatureCache.build(agent, data, 128)        # feat [K,n,128] once, encoders frozen
+      trainer = HeadTrainer(agent, lr=1e-3)
+      losses = trainer.train_epoch(cache, 128, generator=g)      # [K] per-member epoch losses
+      trainer.publish(agent)                                     # the new weights into the live agent, on the device
+
+  The head is `_merger` and `_decoder` (32 164 of the 2.4 M parameters, the tail of `arch.packed_spec()`); the encoder
+  is frozen in eval mode, so its output per (member, observation) is a constant, there is no BatchNorm and no dropout,
+  and the loss of a member is the reference's `-mean(log_prob - logabsdet)` (dim/train.py:198-204) on targets perturbed
+  with N(0, noise_level^2) noise (train.py:184-189).  The step is deterministic by construction (no float atomics; sums
+  over the rows in an order fixed by the batch size alone) and member k's results do not depend on K.
+
+  State, all on the agent's device: `params` [K, P_head] (contiguous, what Adam steps), `grads`, `exp_avg`,
+  `exp_avg_sq` of that shape, `step_count`, and `full` [K, packed_numel]: each member's whole packed vector, its
+  encoder part as the agent's models had it at construction.  `params` is a tensor of its own, not a view of `full`
+  (one Adam launch needs the K heads contiguous); `publish`, `state_dict` and `sync_to_models` copy it into `full`'s
+  tail first.  There is no CPU path."""
+
+  def __init__(self, agent, lr: float = 1e-3, weight_decay: float = 0.0, noise_level: float = 1e-2, max_batch: int = 512,
+               betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    if not torch.cuda.is_available():
+      raise RuntimeError("oatomobile_amd.HeadTrainer needs a ROCm device; there is no CPU path.")
+    if max_batch < 1:
+      raise ValueError("max_batch=%d must be >= 1" % max_batch)
+    self._lib = _lib.load()
+    self._device = agent._device
+    self._models = list(agent._models)
+    self._C = agent._in_channels
+    self.K = len(self._models)
+    self.P = int(self._lib.rip_head_numel())
+    spec = arch.packed_spec(self._C)
+    self._head_spec = [(k, s) for k, s in spec if not k.startswith("_encoder.")]
+    if sum(int(np.prod(s)) for _, s in self._head_spec) != self.P or spec[-len(self._head_spec):] != self._head_spec:
+      raise RuntimeError("head layout mismatch: library %d floats, arch.packed_spec tail %d" %
+                         (self.P, sum(int(np.prod(s)) for _, s in self._head_spec)))
+    self._lr, self._wd, self._noise = float(lr), float(weight_decay), float(noise_level)
+    self._betas, self._eps = (float(betas[0]), float(betas[1])), float(eps)
+    self._max_batch = int(max_batch)
+    self.full = torch.from_numpy(np.stack([m.packed_weights() for m in self._models])).to(self._device)
+    self.params = self.full[:, -self.P:].clone()
+    self.grads = torch.zeros_like(self.params)
+    self.exp_avg = torch.zeros_like(self.params)
+    self.exp_avg_sq = torch.zeros_like(self.params)
+    self.step_count = 0
+    self._workspace = torch.empty(int(self._lib.rip_head_workspace_bytes(self.K, self._max_batch)), dtype=torch.uint8,
+                                  device=self._device)
+    self.q_rows = self.z = None
+
+  # ---- one step ----
+  def _check(self, feat, vec, target, y, rows, noise):
+    name = "HeadTrainer"
+    for what, t in (("feat", feat), ("vec", vec), ("target", target), ("y", y), ("rows", rows), ("noise", noise)):
+      if t is None:
+        continue
+      if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self._device:
+        raise RuntimeError("%s: `%s` must be a tensor on %s (got %s) — no CPU path" %
+                           (name, what, self._device, getattr(t, "device", type(t))))
+    if feat.dim() != 3 or feat.shape[0] != self.K:
+      raise ValueError("%s: feat must have shape [K=%d,n,%d], got %s" % (name, self.K, arch.NUM_FEATURES, tuple(feat.shape)))
+    _lib.expect_shape(feat, (self.K, None, arch.NUM_FEATURES), "feat")
+    n = int(feat.shape[1])
+    _lib.expect_shape(vec, (n, arch.VECTOR_INPUTS), "vec")
+    if rows is not None:
+      if rows.dtype != torch.int64:
+        raise ValueError("%s: rows must be int64, got %s" % (name, rows.dtype))
+      _lib.expect_shape(rows, (self.K, None), "rows")
+    B = n if rows is None else int(rows.shape[1])
+    if B < 1 or B > self._max_batch:
+      raise ValueError("%s: batch of %d rows outside [1, max_batch=%d]" % (name, B, self._max_batch))
+    if (y is None) == (target is None):
+      raise ValueError("%s: pass exactly one of `y` [K,B,4,2] and `target` [n,L,2]" % name)
+    if y is not None:
+      _lib.expect_shape(y, (self.K, B, arch.T, 2), "y")
+      if noise is not None:
+        raise ValueError("%s: `noise` goes with `target`; a dense `y` is taken as it is" % name)
+    else:
+      _lib.expect_shape(target, (n, None, 2), "target")
+      if noise is not None:
+        _lib.expect_shape(noise, (self.K, B, arch.T, 2), "noise")
+    return n, B
+
+  def backward(self, feat: torch.Tensor, vec: torch.Tensor, *, target: Optional[torch.Tensor] = None,
+               y: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+               perturb: bool = True, gradients: bool = True) -> torch.Tensor:
+    """Forward and backward of the K heads; the gradients land in `self.grads`, `q = log_prob - logabsdet` per row in
+    `self.q_rows` [K,B] and the merger's output in `self.z` [K,B,64].  Returns the losses [K] (a fresh device tensor).
+
+    `feat` [K,n,128] and `vec` [n,5] are the cached features and vector inputs of n observations; `rows` [K,B] int64
+    picks each member's batch out of them (repeats allowed; None = all n rows in order for every member).  The target
+    is either `y` [K,B,4,2], taken as it is, or `target` [n,L,2], the cached futures, gathered as
+    `target[rows, 0::L // 4]` inside the kernel plus `noise` [K,B,4,2] (None with `perturb`: drawn here as
+    N(0, noise_level^2) from torch's default device generator; `perturb=False`: none).  A row outside [0, n) gives that
+    member a NaN loss and NaN gradients and leaves the other members alone.  `gradients=False`: forward only."""
+    n, B = self._check(feat, vec, target, y, rows, noise)
+    L = stride = 0
+    if target is not None:
+      L = int(target.shape[1])
+      from oatomobile_amd.replay import downsample_stride
+      stride = downsample_stride(L, arch.T)
+      if noise is None and perturb and self._noise > 0.0:
+        noise = torch.empty(self.K, B, arch.T, 2, device=self._device).normal_(0.0, self._noise)
+    self.q_rows = torch.empty(self.K, B, device=self._device)
+    self.z = torch.empty(self.K, B, arch.HIDDEN_SIZE, device=self._device)
+    loss = torch.empty(self.K, device=self._device)
+    _lib.check(self._lib.rip_head_forward_backward(
+        _lib.ptr(self.params), _lib.ptr(self.grads if gradients else None), _lib.ptr(feat), _lib.ptr(vec), n,
+        _lib.ptr(rows, torch.int64), _lib.ptr(y), _lib.ptr(target), L, stride, _lib.ptr(noise), self.K, B, self._max_batch,
+        _lib.ptr(self._workspace, torch.uint8), _lib.ptr(self.q_rows), _lib.ptr(loss), _lib.ptr(self.z),
+        _lib.current_stream(self._device)))
+    return loss
+
+  def apply(self) -> None:
+    """`optimizer.step()` (torch.optim.Adam) for the K heads: one `rip_train_adam` on the flattened [K * P_head]."""
+    self.step_count += 1
+    _lib.check(self._lib.rip_train_adam(
+        _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), None,
+        self.params.numel(), self.step_count, self._lr, self._betas[0], self._betas[1], self._eps, self._wd,
+        _lib.current_stream(self._device)))
+
+  def train_step(self, feat, vec, *, target=None, y=None, rows=None, noise=None) -> torch.Tensor:
+    """`backward` + `apply`; returns the losses [K] before the step."""
+    loss = self.backward(feat, vec, target=target, y=y, rows=rows, noise=noise)
+    self.apply()
+    return loss
+
+  def evaluate_step(self, feat, vec, *, target=None, y=None, rows=None) -> torch.Tensor:
+    """Forward only on the unperturbed target: `q_rows` [K,B] (the losses are `-q_rows.mean(1)`)."""
+    self.backward(feat, vec, target=target, y=y, rows=rows, perturb=False, gradients=False)
+    return self.q_rows
+
+  def train_epoch(self, features, batch_size: int, *, generator: Optional[torch.Generator] = None,
+                  member_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One epoch over `features` (a `replay.FeatureCache`) with `DataLoader(shuffle=True, drop_last=False)` semantics,
+    like `DIMTrainer.train_epoch`: `train_step` per batch, the last short batch included, and the mean of the
+    per-batch losses per member, [K] on the device (no synchronisation).
+
+    `member_rows` [K,m] int64 maps each member's epoch onto its own m cache rows (a bootstrap sample: repeats allowed);
+    None = every member sees all n rows.  The random draws come from `generator` (a generator on this device; None =
+    torch's default one) in this order: `torch.randperm(m)` once (kept in `self.last_permutation`; all members share
+    it, over their own rows), then per batch the target noise N(0, noise_level^2) of shape [K, rows, 4, 2].  No batch
+    is assembled: the kernel reads the cache rows through the index table."""
+    if batch_size < 1 or batch_size > self._max_batch:
+      raise ValueError("batch_size=%d outside [1, max_batch=%d]" % (batch_size, self._max_batch))
+    if features.feat.shape[0] != self.K:
+      raise ValueError("the feature cache holds %d members, the trainer %d" % (features.feat.shape[0], self.K))
+    n = int(features.feat.shape[1])
+    if member_rows is not None:
+      if not isinstance(member_rows, torch.Tensor) or member_rows.dtype != torch.int64 or member_rows.device != self._device:
+        raise ValueError("member_rows must be an int64 tensor on %s" % (self._device,))
+      _lib.expect_shape(member_rows, (self.K, None), "member_rows")
+    m = n if member_rows is None else int(member_rows.shape[1])
+    perm = torch.randperm(m, device=self._device, generator=generator)
+    self.last_permutation = perm
+    losses = []
+    for g0 in range(0, m, batch_size):
+      idx = perm[g0:g0 + batch_size]
+      rows = (idx.unsqueeze(0).expand(self.K, -1) if member_rows is None else member_rows[:, idx]).contiguous()
+      noise = torch.empty(self.K, idx.numel(), arch.T, 2, device=self._device).normal_(0.0, self._noise, generator=generator)
+      losses.append(self.train_step(features.feat, features.vec, target=features.future, rows=rows, noise=noise))
+    self.last_epoch_losses = torch.stack(losses) if losses else torch.zeros(0, self.K, device=self._device)
+    return self.last_epoch_losses.mean(0) if losses else torch.full((self.K,), float("nan"), device=self._device)
+
+  # ---- the trained weights ----
+  def _sync_full(self) -> None:
+    self.full[:, -self.P:].copy_(self.params)
+
+  def named_gradients(self, k: int):
+    """`{state_dict key: gradient view}` of member `k`'s head."""
+    return self._unpack(self.grads[k])
+
+  def _unpack(self, vector: torch.Tensor):
+    out, pos = {}, 0
+    for key, shape in self._head_spec:
+      cnt = int(np.prod(shape))
+      out[key] = vector[pos:pos + cnt].view(*shape)
+      pos += cnt
+    return out
+
+  def state_dict(self, k: int):
+    """Member `k`'s weights as a reference-compatible `state_dict`: the encoder entries (and the BatchNorm counters) are
+    the model's, the head entries the trainer's."""
+    sd = {key: v.detach().clone() for key, v in self._models[k].state_dict().items()}
+    for key, v in self._unpack(self.params[k]).items():
+      sd[key] = v.detach().clone()
+    return sd
+
+  def publish(self, agent, members=None) -> None:
+    """`agent.load_member(k, self.full[k])` for every member (or those of `members`): the trained heads into a live
+    `RIPAgent` on the device, behind the steps already issued on the current stream.  The agent's captured
+    one-observation pipelines stay unless a member's `split_wmax` flag changes (`RIPAgent.load_member`); the models are
+    not touched (`sync_to_models`)."""
+    self._sync_full()
+    for k in (range(self.K) if members is None else members):
+      agent.load_member(int(k), self.full[int(k)])
+
+  def sync_to_models(self) -> None:
+    """Writes the trained heads into the agent's `ImitativeModel`s (every agent holding them re-uploads on its next call)."""
+    for k, m in enumerate(self._models):
+      m.load_state_dict({key: v.to(m.device) for key, v in self.state_dict(k).items()}, strict=True)
